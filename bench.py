@@ -9,13 +9,18 @@ Lagrangian Hessian).  `value` times the PRODUCT FUNCTION: one call
 max_iter=K)`` -- its priming (qp_subproblem.py:502-512), the batched device
 loop, its state reads, the result -- with a finite trust radius that is never
 reached (how the SQP calls it: the norm test of qp_subproblem.py:583 is formed
-and taken every iteration), so exactly K iterations execute.  The bare device
-loop (one C call, no priming: the headline of rounds 1-3) is reported as
-`device_loop_only`, the same loop with trust_radius=inf (the norm test cannot
-trigger and is not formed) as `unbounded_trust_region`.  All inputs are
-resident in HBM when the timed region starts.
+and taken every iteration), so exactly K iterations execute, in one timed
+region after a warm-up call of W iterations and WARM_S seconds of untimed
+regions like it.  All inputs are resident in HBM when the timed region starts.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1000000] [--m 100000]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only that: set-up, warm-up, the K timed iterations, one JSON
+line.  --dump-outputs DIR then writes what the last timed call returned (x and
+its info entries) as DIR/<name>.npy; the instance is seeded, so the same
+arguments give the same inputs in every run.  --full adds, after the headline,
+every side measurement listed below; the --no-* options leave some of them out.
 
 N > 1 runs one rank per GPU: under torch.distributed.run (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment), or -- started directly, the way
@@ -29,8 +34,11 @@ time over ranks ("strong" scaling).  The JSON also carries the measured
 latency floor of those collectives, a weak-scaling point (n = N * 1e6) and the
 whole config-4 solve on the sharded backend.
 
-Prints ONE JSON line (see the driver contract in the task statement) with
-`roofline` for the dominant kernel (step2 fused into the H.p CSR SpMV),
+Prints ONE JSON line; with --full (N = 1) it also carries `timed_regions`
+(the headline's region and four more like it), `device_loop_only` (the bare
+device loop: one C call, no priming, the headline of rounds 1-3),
+`unbounded_trust_region` (that loop with trust_radius=inf: the norm test is not
+formed), `roofline` for the dominant kernel (step2 fused into the H.p CSR SpMV),
 `roofline_out_of_cache` (the same measurement at n=4e6, past the Infinity
 Cache), `loop_kernels` (per kernel: algorithmic bytes, PMC bytes moved, their
 ratio), `public_api` (the product function over several calls, both radii),
@@ -132,19 +140,12 @@ def loop_bytes(n, m, nnzA, nnzH, fused_step1=True, fused_step2=True, fused_tail=
     return algo, sum(algo.values()) + 4 * 8 * m
 
 
-def single_gpu_measure(A_h, H_h, hdiag_h, c_h, n, m, K, W, repeats=20):
-    """Upload one subproblem, factor, prime the device loop like projected_cg does, then
-    W warm-up + EXACTLY K timed iterations (the contract's region), `repeats` further K-step
-    regions (median / min / max), HIP-event attribution per kernel, and the dominant kernel
-    on its own.  The timed workload has a FINITE trust radius that is never reached (1e300):
-    ||x + alpha p||^2 is formed and tested every iteration, as in every call the SQP makes;
-    the trust_radius=inf variant (test not formed) is measured after it."""
-    import numpy as np
+def upload(A_h, H_h, hdiag_h, c_h, n, m):
+    """One subproblem on the device with its projections factored (untimed set-up)."""
     import torch
-    from ipsolver import _hip, cg_fused, projector
+    from ipsolver import projector
     from ipsolver import device as dv
     from ipsolver.operators import DeviceHessian
-    lib = _hip.load()
     A = dv.DeviceCSR.from_scipy(A_h)
     H = DeviceHessian(n, csr=dv.DeviceCSR.from_scipy(H_h), diag=dv.DVec.from_host(hdiag_h))
     c = dv.DVec.from_host(c_h)
@@ -153,7 +154,22 @@ def single_gpu_measure(A_h, H_h, hdiag_h, c_h, n, m, K, W, repeats=20):
     t0 = time.time()
     Z, LS, Y = projector.projections(A)
     torch.cuda.synchronize()
-    t_factor = time.time() - t0
+    return {"A": A, "H": H, "c": c, "b": b, "Z": Z, "Y": Y, "t_factor": time.time() - t0}
+
+
+def single_gpu_measure(dev, hdiag_h, n, m, K, W, repeats=20):
+    """On a subproblem from ``upload``: prime the device loop like projected_cg does, then
+    W warm-up + EXACTLY K timed iterations, `repeats` further K-step
+    regions (median / min / max), HIP-event attribution per kernel, and the dominant kernel
+    on its own.  The timed workload has a FINITE trust radius that is never reached (1e300):
+    ||x + alpha p||^2 is formed and tested every iteration, as in every call the SQP makes;
+    the trust_radius=inf variant (test not formed) is measured after it."""
+    import numpy as np
+    import torch
+    from ipsolver import _hip, cg_fused
+    from ipsolver import device as dv
+    lib = _hip.load()
+    A, H, c, b, Z, Y = (dev[k] for k in ("A", "H", "c", "b", "Z", "Y"))
     P = Z.projector
 
     # ---- prime the loop exactly like projected_cg does (untimed)
@@ -297,9 +313,7 @@ def single_gpu_measure(A_h, H_h, hdiag_h, c_h, n, m, K, W, repeats=20):
     older = (algo[dom] + 8 * n) / (hp_us * 1e-6) / 1e9 if merged_diag else None
     med_rate = repeat["iterations_per_s"]["median"] if repeat else K / elapsed
     return {
-        "A": A, "H": H, "c": c, "b": b, "Z": Z, "Y": Y, "elapsed": elapsed, "repeat": repeat,
-        "unbounded": unbounded,
-        "t_factor": t_factor, "nnzA": nnzA, "nnzH": nnzH, "dom": dom,
+        "elapsed": elapsed, "repeat": repeat, "unbounded": unbounded, "dom": dom,
         "roofline": {"bound": "hbm", "kernel": dom_label,
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS,
@@ -992,6 +1006,8 @@ def sharded_leg(args, world, rank, A_h, H_h, hdiag_h, c_h, n, m, K, W):
         elapsed, last_segment = _sharded_run(F, primed, K, W, dist, torch)
     calls = {k: v - before[k] for k, v in sh.comm.stats.items()}
     x_sharded = sharded.ShardVec(sharded.HipOps().dv.DVec(F.L.x.clone()), sh, "col").to_host()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x_sharded})
     ab = {transport: {"iterations_per_s": K / elapsed, "ms_per_step": 1e3 * elapsed / K}}
     if ipc_error is not None:
         ab["ipc"] = {"error": ipc_error}
@@ -1243,6 +1259,27 @@ def sharded_leg(args, world, rank, A_h, H_h, hdiag_h, c_h, n, m, K, W):
     dist.destroy_process_group()
 
 
+WARM_S = 0.3                  # seconds of untimed headline regions before the timed one
+DUMP_BYTES = 60 * 10 ** 6     # (64 MB allowed in all: the .npy headers fit in the rest)
+
+
+def dump_outputs(directory, arrays):
+    """``--dump-outputs``: one ``directory/<name>.npy`` (float64) per array, at most DUMP_BYTES
+    in all.  An array too large for that is written as a fixed sample: every k-th entry, the
+    same k for the same arguments."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.size == 1)
+    big = [k for k, a in arrays.items() if a.size > 1]
+    for k in big:
+        a = arrays[k].ravel()
+        cap = max(1, (DUMP_BYTES - small) // len(big) // 8)
+        arrays[k] = a[::-(-a.size // cap)]
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def failure_line(n_gpus, K, W, error, **more):
     """The contract's keys with value 0 and a readable ``error``: a failed N > 1 run must still
     leave one JSON line behind (and a non-zero exit code)."""
@@ -1358,6 +1395,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--n", type=int, default=1000000)
     ap.add_argument("--m", type=int, default=100000)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, also every side measurement (device loop, "
+                         "roofline, public API, per-rank sweep, out-of-cache size, configs 2/3/5 "
+                         "to gtol, CPU baseline); the --no-* options below select among them")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-iters", type=int, default=250)
     ap.add_argument("--no-configs", action="store_true",
@@ -1433,11 +1476,8 @@ def main():
                 sys.stdout.flush()
             raise
 
-    r1 = single_gpu_measure(A_h, H_h, hdiag_h, c_h, n, m, K, W, repeats=args.repeats)
-    A, H, c, b, Z, Y = (r1.pop(k) for k in ("A", "H", "c", "b", "Z", "Y"))
-    traffic, traffic_src = None, None
-    if (n, m) == (1000000, 100000):
-        traffic, traffic_src = stored_traffic(PMC_PROFILE, r1["dom"])
+    dev = upload(A_h, H_h, hdiag_h, c_h, n, m)
+    A, H, c, b, Z, Y = (dev[k] for k in ("A", "H", "c", "b", "Z", "Y"))
     # ---- the headline: the PRODUCT FUNCTION as a user calls it -- ONE call of
     # ipsolver.qp.projected_cg(H, c, Z, Y, b, trust_radius, tol=0, max_iter=K), W warm-up
     # iterations in a call before it, the timed region = the call (synchronised either side):
@@ -1451,21 +1491,34 @@ def main():
     # (with tol = 0 the CG reaches an exactly zero residual after ~500 iterations: a K beyond
     # 200 is run as consecutive calls of <= 200 iterations on the same subproblem)
     chunks = [200] * (K // 200) + ([K % 200] if K % 200 else [])
-    # FIVE timed regions of exactly K steps each (a region at the driver's K = 20 lasts 1 ms:
-    # one sample says little -- VERDICT r4); `value` is their median, every one is reported
-    regions = []
-    for _ in range(5):
+
+    def timed_region():
+        """EXACTLY K iterations of the headline call(s), synchronised either side: (seconds,
+        what the last call returned)."""
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         done = 0
         for kc in chunks:
-            _xk, _info = _qp.projected_cg(H, c, Z, Y, b, trust_radius=1e300, tol=0, max_iter=kc)
-            done += _info["niter"]
+            last = _qp.projected_cg(H, c, Z, Y, b, trust_radius=1e300, tol=0, max_iter=kc)
+            done += last[1]["niter"]
         torch.cuda.synchronize()
-        regions.append(time.perf_counter() - t0)
+        dt = time.perf_counter() - t0
         if done != K:
             raise SystemExit("headline call(s) ran %d iterations instead of %d" % (done, K))
-    elapsed = sorted(regions)[len(regions) // 2]
+        return dt, last
+
+    # The region's own calls, untimed, for WARM_S after the W iterations: regions right after
+    # set-up run a few per cent slower than later ones (at K = 20, n = 1e6: 4-10 %), and the ONE
+    # timed region is to measure the steady state.
+    t_warm = time.perf_counter()
+    while True:
+        timed_region()
+        if time.perf_counter() - t_warm >= WARM_S:
+            break
+    elapsed, (x_last, info_last) = timed_region()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(
+            x=x_last.to_host(), **{k: float(v) for k, v in info_last.items()}))
     result = {
         "metric": "projected-CG iters/sec (fp64) at n=1e6,m=1e5",
         "value": K / elapsed,
@@ -1475,9 +1528,6 @@ def main():
         "warmup": W,
         "ms_per_step": 1e3 * elapsed / K,
         "timed_region_s": elapsed,
-        "timed_regions": {"what": "value = the median of these regions of exactly `steps` "
-                                  "iterations each (barrier + synchronise either side of each)",
-                          "iterations_per_s": [K / t for t in regions]},
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -1491,8 +1541,27 @@ def main():
                                "finite trust radius that is never reached (the norm test of "
                                "qp_subproblem.py:583 formed every iteration, as in the SQP's "
                                "calls; trust_radius=inf: see unbounded_trust_region)",
-                   "n": n, "m": m, "nnz_A": r1["nnzA"], "nnz_H": r1["nnzH"],
+                   "n": n, "m": m, "nnz_A": A.pattern.nnz, "nnz_H": H.csr.pattern.nnz,
                    "parallelism": "single GPU"},
+        "kernel_source_hash": kernel_source_hash(),
+        "setup_s": {"generate_host": t_gen, "factor_device": dev["t_factor"]},
+    }
+    if not args.full:
+        print(json.dumps(result))
+        return
+
+    # ---- --full: everything below is measured after the headline and leaves it unchanged
+    regions = [elapsed] + [timed_region()[0] for _ in range(4)]
+    result["timed_regions"] = {
+        "what": "the headline's region (value) and four more like it: exactly `steps` "
+                "iterations each (synchronise either side of each)",
+        "iterations_per_s": [K / t for t in regions],
+        "median_iterations_per_s": K / sorted(regions)[len(regions) // 2]}
+    r1 = single_gpu_measure(dev, hdiag_h, n, m, K, W, repeats=args.repeats)
+    traffic, traffic_src = None, None
+    if (n, m) == (1000000, 100000):
+        traffic, traffic_src = stored_traffic(PMC_PROFILE, r1["dom"])
+    result.update({
         "device_loop_only": {
             "what": "the bare device loop: ipx_cg_iterate enqueues exactly `steps` iterations of "
                     "the primed subproblem in one C call (rounds 1-3's headline); no priming, no "
@@ -1505,10 +1574,7 @@ def main():
                          traffic / (r1["roofline"]["avg_launch_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS),
         "loop_kernels": traffic_table(PMC_PROFILE, r1["whole_iteration"]["algorithmic_bytes_per_kernel"])
         if (n, m) == (1000000, 100000) else None,
-        "whole_iteration": r1["whole_iteration"],
-        "kernel_source_hash": kernel_source_hash(),
-        "setup_s": {"generate_host": t_gen, "factor_device": r1["t_factor"]},
-    }
+        "whole_iteration": r1["whole_iteration"]})
     # ---- the product function as a user calls it
     result["public_api"] = public_api_leg(H, c, Z, Y, b, K)
     # (b = None -- the extension the SQP's own call uses, equality_constrained_sqp.py:126 passes
@@ -1541,8 +1607,9 @@ def main():
         probb = CenteredBandedNLP(nb, mb, seed=0)
         xb = probb.x0
         vb = 0.1 * np.random.default_rng(7).standard_normal(mb)
-        rb = single_gpu_measure(probb.constr_jac(xb), probb.hess(xb), probb.kappa * probb.Wt.dot(vb),
-                                probb.grad(xb), nb, mb, K, W, repeats=min(args.repeats, 5))
+        hdiag_b = probb.kappa * probb.Wt.dot(vb)
+        devb = upload(probb.constr_jac(xb), probb.hess(xb), hdiag_b, probb.grad(xb), nb, mb)
+        rb = single_gpu_measure(devb, hdiag_b, nb, mb, K, W, repeats=min(args.repeats, 5))
         traffic_b, src_b = stored_traffic(PMC_PROFILE_BIG, rb["dom"])
         result["roofline_out_of_cache"] = dict(
             rb["roofline"], traffic=traffic_b, traffic_source=src_b, n=nb, m=mb,
@@ -1553,7 +1620,7 @@ def main():
         if isinstance(result.get("measured_stream"), dict) and "axpby_2r1w" in result["measured_stream"]:
             result["roofline_out_of_cache"]["frac_of_measured_stream"] = \
                 result["roofline_out_of_cache"]["achieved"] / result["measured_stream"]["axpby_2r1w"]
-        del rb, probb
+        del rb, devb, probb
         torch.cuda.empty_cache()
 
     # ---- second half of the metric: wall-clock of the whole config-3 solve to

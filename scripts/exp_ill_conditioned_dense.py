@@ -1,5 +1,5 @@
 import os, sys
-ROOT = "/root/repo" if os.path.exists("/root/repo/tests") else os.getcwd()
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "ip-nonlinear-solver_amd"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 import numpy as np, scipy.linalg

@@ -1,7 +1,7 @@
 """Per-kernel launch durations grouped by grid size from a rocprofv3 kernel trace of bench.py
 (the bench runs the loop at n=1e6 and n=4e6: the same kernel appears with two grids).
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/benchprof -- python3 bench.py
-    python scripts/kernel_durations_by_size.py gpurun_out/benchprof profiles/<name>.json"""
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/benchprof -- python3 bench.py --full
+    python scripts/kernel_durations_by_size.py /tmp/benchprof profiles/<name>.json"""
 import collections, csv, glob, json, os, statistics, sys
 d, out = sys.argv[1:3]
 f = max(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True), key=os.path.getmtime)

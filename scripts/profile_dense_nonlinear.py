@@ -1,5 +1,6 @@
 import cProfile, os, pstats, sys, time, warnings, io
-sys.path.insert(0, "/root/repo/ip-nonlinear-solver_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                "ip-nonlinear-solver_amd"))
 import torch, ipsolver
 from ipsolver.synthetic import DenseDeviceCallbacks
 warnings.simplefilter("ignore")

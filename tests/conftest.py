@@ -1,3 +1,4 @@
+import glob
 import json
 import os
 import sys
@@ -12,6 +13,18 @@ for p in (ROOT, PKG, os.path.dirname(os.path.abspath(__file__))):
         sys.path.insert(0, p)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def load_npz(name):
+    """tests/golden/<name>.npz as a dict, or the same arrays from its parts <name>.part<k>.npz
+    (make_golden.savez_parts splits a fixture that would exceed 1 MiB)."""
+    paths = sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz")),
+                   key=lambda p: int(p[len(os.path.join(GOLDEN, name + ".part")):-len(".npz")]))
+    out = {}
+    for path in paths or [os.path.join(GOLDEN, name + ".npz")]:
+        with np.load(path) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out
 
 
 def pytest_configure(config):
@@ -52,12 +65,12 @@ def e2e_golden():
 
 @pytest.fixture(scope="session")
 def banded2000():
-    return dict(np.load(os.path.join(GOLDEN, "banded_n2000.npz")))
+    return load_npz("banded_n2000")
 
 
 @pytest.fixture(scope="session")
 def banded20000():
-    return dict(np.load(os.path.join(GOLDEN, "banded_n20000.npz")))
+    return load_npz("banded_n20000")
 
 
 @pytest.fixture(scope="session")
@@ -68,7 +81,7 @@ def qp_extra():
 
 @pytest.fixture(scope="session")
 def banded_refine2000():
-    return dict(np.load(os.path.join(GOLDEN, "banded_refine_n2000.npz")))
+    return load_npz("banded_refine_n2000")
 
 
 @pytest.fixture(scope="session")

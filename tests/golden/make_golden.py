@@ -11,7 +11,8 @@ LinearOperator with an int8 vector, which breaks the reference's
 ``np.zeros_like(p); result += ...`` accumulation, so ``dtype=float`` is
 defaulted for operators built from a bare matvec.  Numerics are untouched.
 
-Outputs (numbers only -- no reference source travels):
+Outputs (numbers only -- no reference source travels; an .npz over 1 MiB is written as
+<name>.part0.npz, <name>.part1.npz, ...: ``savez_parts``):
   qp_small.json     reference outputs for every case in tests/cases_small.py
   banded_*.npz      projected_cg / modified_dogleg / Z,LS,Y traces on the
                     seeded banded problem
@@ -103,6 +104,33 @@ def jf(v):
     if isinstance(v, (list, tuple)):
         return [jf(t) for t in v]
     raise TypeError(type(v))
+
+
+PART_BYTES = 960 << 10     # no committed file over 1 MiB
+
+
+def savez_parts(path, **arrays):
+    """np.savez_compressed to ``path``, or -- when that file would exceed PART_BYTES -- to
+    ``<stem>.part0.npz``, ``<stem>.part1.npz``, ... with the arrays in the same order
+    (tests/conftest.py ``load_npz`` joins them)."""
+    import io
+
+    def size(d):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **d)
+        return buf.tell()
+    parts, cur = [], {}
+    for k, v in arrays.items():
+        if cur and size(dict(cur, **{k: v})) > PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = v
+    parts.append(cur)
+    if len(parts) == 1:
+        np.savez_compressed(path, **arrays)
+        return
+    for i, part in enumerate(parts):
+        np.savez_compressed("%s.part%d.npz" % (path[:-len(".npz")], i), **part)
 
 
 def small_cases():
@@ -548,8 +576,7 @@ def main():
         return
     if "--late-barrier" in sys.argv:
         for n, m, k in ((400, 40, 6), (12000, 1200, 4)):
-            np.savez_compressed(os.path.join(HERE, "late_barrier_n%d.npz" % n),
-                                **late_barrier(n, m, k))
+            savez_parts(os.path.join(HERE, "late_barrier_n%d.npz" % n), **late_barrier(n, m, k))
         return
     if "--e2e" in sys.argv:
         with open(os.path.join(HERE, "e2e.json"), "w") as f:
@@ -653,12 +680,9 @@ def main():
     print("banded traces ...")
     with open(os.path.join(HERE, "qp_extra.json"), "w") as f:
         json.dump(extra_cases(), f)
-    np.savez_compressed(os.path.join(HERE, "banded_n2000.npz"),
-                        **banded_traces(2000, 200, True))
-    np.savez_compressed(os.path.join(HERE, "banded_refine_n2000.npz"),
-                        **banded_refine_traces(2000, 200))
-    np.savez_compressed(os.path.join(HERE, "banded_n20000.npz"),
-                        **banded_traces(20000, 2000, False))
+    savez_parts(os.path.join(HERE, "banded_n2000.npz"), **banded_traces(2000, 200, True))
+    savez_parts(os.path.join(HERE, "banded_refine_n2000.npz"), **banded_refine_traces(2000, 200))
+    savez_parts(os.path.join(HERE, "banded_n20000.npz"), **banded_traces(20000, 2000, False))
     print("end-to-end ...")
     with open(os.path.join(HERE, "e2e.json"), "w") as f:
         json.dump(e2e(), f)

@@ -915,15 +915,15 @@ def test_bench_launcher_reports_a_failing_rank():
 
 
 def test_bench_contract_with_odd_step_counts():
-    """``bench.py --steps K --warmup W`` for a K that is no divisor of anything (the driver
-    chooses K and W): one JSON line with the contract's keys, the roofline and CPU-baseline
-    objects, the finite-radius figure next to the headline."""
+    """``bench.py --full --steps K --warmup W`` for a K that is no divisor of anything (the
+    driver chooses K and W): one JSON line with the contract's keys, the roofline and
+    CPU-baseline objects, the finite-radius figure next to the headline."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "7",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "7",
                           "--warmup", "3", "--no-big", "--repeats", "2", "--cpu-iters", "20"],
                          cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -939,6 +939,63 @@ def test_bench_contract_with_odd_step_counts():
     assert d["unbounded_trust_region"]["iterations_per_s"] > d["value"] * 0.9
     assert d["public_api"]["trust_radius_finite"]["iterations_per_s"] > 1000
     assert d["parity_vs_oracle"]["max_rel_err"] < 1e-10
+    assert len(d["timed_regions"]["iterations_per_s"]) == 5
+    assert d["timed_regions"]["iterations_per_s"][0] == d["value"]
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain ``bench.py --steps K --warmup W --dump-outputs DIR``: the headline alone (none
+    of the --full measurements), and what the last timed call returned -- x and its info --
+    as DIR/<name>.npy; two runs with the same arguments write the same arrays, and x is the
+    public call's on the same seeded instance."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, m, K = 20000, 2000, 9
+    dumps = []
+    for run in range(2):
+        d_out = str(tmp_path / ("run%d" % run))
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(K),
+                              "--warmup", "2", "--n", str(n), "--m", str(m),
+                              "--dump-outputs", d_out],
+                             cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == K and d["warmup"] == 2 and d["value"] > 0
+        assert d["ms_per_step"] == pytest.approx(1e3 * d["timed_region_s"] / K)
+        for key in ("metric", "unit", "higher_is_better", "dtype"):
+            assert key in d, key
+        for key in ("roofline", "cpu_baseline", "public_api", "timed_regions",
+                    "wall_clock_to_gtol"):
+            assert key not in d, key
+        got = {f[:-4]: np.load(os.path.join(d_out, f)) for f in sorted(os.listdir(d_out))}
+        assert sorted(got) == ["hits_boundary", "niter", "stop_cond", "x"]
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert got["x"].shape == (n,) and np.all(np.isfinite(got["x"]))
+        assert int(got["niter"]) == K
+        dumps.append(got)
+    from conftest import close
+    for k in ("hits_boundary", "niter", "stop_cond"):
+        assert dumps[0][k] == dumps[1][k], k
+    close(dumps[1]["x"], dumps[0]["x"], 1e-13)
+    # the same call in this process, on the instance bench.py builds
+    from ipsolver import device as dv, projector, qp
+    from ipsolver.operators import DeviceHessian
+    from ipsolver.synthetic import CenteredBandedNLP
+    prob = CenteredBandedNLP(n, m, seed=0)
+    v = 0.1 * np.random.default_rng(7).standard_normal(m)
+    A = dv.DeviceCSR.from_scipy(prob.constr_jac(prob.x0))
+    H = DeviceHessian(n, csr=dv.DeviceCSR.from_scipy(prob.hess(prob.x0)),
+                      diag=dv.DVec.from_host(prob.kappa * prob.Wt.dot(v)))
+    Z, _, Y = projector.projections(A)
+    x, info = qp.projected_cg(H, dv.DVec.from_host(prob.grad(prob.x0)), Z, Y, dv.DVec.zeros(m),
+                              trust_radius=1e300, tol=0, max_iter=K)
+    assert info["niter"] == K
+    close(x, dumps[0]["x"], 1e-12)
 
 
 @pytest.mark.parametrize("what", ["config4:equality_constrained_sqp", "config4:tr_interior_point",

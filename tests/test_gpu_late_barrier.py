@@ -32,7 +32,7 @@ import pytest
 import scipy.sparse as sps
 
 from banded_setup import load_synthetic
-from conftest import GOLDEN
+from conftest import load_npz
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +40,7 @@ SIZES = {400: 6, 12000: 4}
 
 
 def _gold(n):
-    return dict(np.load(os.path.join(GOLDEN, "late_barrier_n%d.npz" % n)))
+    return load_npz("late_barrier_n%d" % n)
 
 
 def _pieces(gold, j):
