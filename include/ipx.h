@@ -191,6 +191,31 @@ int ipx_aat_dense(int64_t m, const int32_t *rowptr, const int32_t *colidx, const
 int ipx_chol_factor(int64_t M, double *G, int *flag, double *work, void *stream);
 int ipx_chol_inverse(int64_t M, double *G, double *X, void *stream);
 
+/* ---- dense constraint Jacobians with inequality rows (csrc/densejac.hip; device-callback
+ * mode's dense canonical form, _canonical_constraint.py:240-280, :363-438, and the barrier's
+ * augmented Jacobian, tr_interior_point.py:141-194).  Row-major, explicit leading dimensions.
+ * out[dst[r], col0 + j] = sign[r] * src[idx[r], j], r < rows, j < ncols; idx / sign / dst may
+ * each be NULL (r, 1, r).  Row selection, re-signing and stacking of several parts. */
+int ipx_dense_gather_rows(int64_t rows, int64_t ncols, const double *src, int64_t lds,
+                          const int32_t *idx, const double *sign, const int32_t *dst,
+                          double *out, int64_t ldo, int64_t col0, void *stream);
+/* out[dst[r], 0:ncols] = sign[r] * (row idx[r] of the CSR matrix, densified) */
+int ipx_csr_rows_to_dense(int64_t rows, int64_t ncols, const int32_t *rowptr,
+                          const int32_t *colidx, const double *val, const int32_t *idx,
+                          const double *sign, const int32_t *dst, double *out, int64_t ldo,
+                          void *stream);
+/* A = [[J_eq, 0], [J_in, diag(s)]], (m_eq + m_in) x (n + m_in), leading dimension n + m_in;
+ * At (optional) = A', leading dimension m_eq + m_in, written in the same pass; A may be NULL
+ * when At is not (the transpose alone). */
+int ipx_dense_augment(int64_t m_eq, int64_t m_in, int64_t n, const double *J_eq, int64_t ld_eq,
+                      const double *J_in, int64_t ld_in, const double *s, double *A, double *At,
+                      void *stream);
+/* G = G0 + diag(0_{m_eq}, s*s) on the M x M layout, M = ipx_dense_padded(m), s[k] at
+ * s + k * incs; G0 NULL: in place.  (A A' for A = [[J_eq, 0], [J_in, diag(s)]] from the Gram
+ * of its first n columns; s read off A's diagonal block with incs = n + m_in + 1.) */
+int ipx_gram_shift(int64_t m, int64_t m_eq, const double *G0, const double *s, int64_t incs,
+                   double *G, void *stream);
+
 /* ---- banded SPD solve with S = A A' (normal equations, projections.py:58-90;
  * replaces SuperLU solve :102,120 / CHOLMOD :62).  Partitioned (SPIKE-style)
  * LDL': see csrc/banded.hip.  Half bandwidth <= ipx_banded_kmax(). */

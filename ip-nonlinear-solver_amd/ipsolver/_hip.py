@@ -43,6 +43,10 @@ _SIGNATURES = {
     "ipx_aat_dense": [_I64, _P, _P, _P, _P, _P],
     "ipx_chol_factor": [_I64, _P, _P, _P, _P],
     "ipx_chol_inverse": [_I64, _P, _P, _P],
+    "ipx_dense_gather_rows": [_I64, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P],
+    "ipx_csr_rows_to_dense": [_I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    "ipx_dense_augment": [_I64, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P],
+    "ipx_gram_shift": [_I64, _I64, _P, _P, _I64, _P, _P],
     "ipx_dot": [_I64, _P, _P, _P, _P, _P],
     "ipx_norms": [_I64, _P, _P, _P, _P],
     "ipx_box_inside": [_I64, _P, _P, _P, _P, _P, _P],

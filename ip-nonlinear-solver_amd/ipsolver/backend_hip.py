@@ -354,10 +354,24 @@ def augmented_jacobian(J_eq, J_ineq, s, n_vars, n_eq, n_ineq):
         idx = torch.from_numpy(slots.astype(np.int32)).to(ctx().device)
         _hip.call("ipx_scatter", n_ineq, _p(s.t), _p(idx), _p(A.val), stream_ptr())
         return A
-    s_h = s.to_host()
-    top = np.hstack((np.atleast_2d(J_eq).reshape(n_eq, n_vars), np.zeros((n_eq, n_ineq))))
-    bot = np.hstack((np.atleast_2d(J_ineq).reshape(n_ineq, n_vars), np.diag(s_h)))
-    return DeviceDense.from_host(np.vstack((top, bot)))
+    from . import dense
+    if isinstance(J_eq, DeviceDense) and isinstance(J_ineq, DeviceDense):
+        # device-callback mode: row-slice views of one stacked buffer (device_mode.DenseStack);
+        # the result carries the structure its normal matrix is formed from
+        return dense.augment(J_eq.t, J_ineq.t, s, n_vars, n_eq, n_ineq,
+                             stack=getattr(J_ineq, "stack", None))
+    # host callbacks: the two blocks go up as they are, the slacks never come down; the same
+    # numbers as np.vstack((np.hstack((J_eq, 0)), np.hstack((J_ineq, diag(s))))), and a plain
+    # DeviceDense (its normal matrix is the Gram of the whole augmented matrix, as before)
+    return dense.augment(_dense_upload(J_eq, n_eq, n_vars), _dense_upload(J_ineq, n_ineq, n_vars),
+                         s, n_vars, n_eq, n_ineq)
+
+
+def _dense_upload(J, rows, n_vars):
+    J = np.ascontiguousarray(np.atleast_2d(np.asarray(J, dtype=np.float64)).reshape(rows, n_vars))
+    if rows == 0:
+        return torch.empty((0, n_vars), dtype=torch.float64, device=ctx().device)
+    return DeviceDense.from_host(J).t
 
 
 # ---- the trust-region subproblem (HIP kernels) ---------------------------

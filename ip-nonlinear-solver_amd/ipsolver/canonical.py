@@ -179,6 +179,43 @@ def _stack_dense(pairs):
     return (np.vstack([dense(p[0]) for p in pairs]), np.vstack([dense(p[1]) for p in pairs]))
 
 
+class DenseRowPlan:
+    """Where every canonical row of a list of constraints lands in ONE dense buffer
+    ``[J_ineq; J_eq]`` (``m_ineq + m_eq`` rows): the row selection, sign flips and stacking of
+    ``_RowMap.dense_jac`` + ``_stack_dense`` as tables, built once per specification (symbolic
+    work).  ``parts[p] = (src, sign, dst)``: row ``dst[r]`` of the buffer is ``sign[r]`` times
+    row ``src[r]`` of part p's Jacobian (``sign`` None: all +1).  The device-callback mode
+    applies it with csrc/densejac.hip; ``apply`` is the same on the host."""
+
+    def __init__(self, row_maps):
+        """``row_maps``: per constraint ``(eq, ineq, sign)`` as ``parse_constraint`` gives them."""
+        self.m_ineq = sum(len(ineq) for _, ineq, _ in row_maps)
+        self.m_eq = sum(len(eq) for eq, _, _ in row_maps)
+        self.parts = []
+        off_ineq, off_eq = 0, self.m_ineq
+        for eq, ineq, sign in row_maps:
+            eq, ineq = np.asarray(eq, dtype=np.int64), np.asarray(ineq, dtype=np.int64)
+            src = np.concatenate((ineq, eq))
+            dst = np.concatenate((off_ineq + np.arange(len(ineq)), off_eq + np.arange(len(eq))))
+            sg = np.concatenate((np.asarray(sign, dtype=float).reshape(-1),
+                                 np.ones(len(eq))))
+            self.parts.append((src, None if np.all(sg == 1) else sg, dst))
+            off_ineq += len(ineq)
+            off_eq += len(eq)
+
+    @property
+    def m(self):
+        return self.m_ineq + self.m_eq
+
+    def apply(self, jacobians, n_vars):
+        """The buffer for the parts' Jacobians (dense arrays or scipy sparse matrices)."""
+        out = np.empty((self.m, n_vars))
+        for J, (src, sign, dst) in zip(jacobians, self.parts):
+            rows = J[src].toarray() if sps.issparse(J) else np.atleast_2d(J)[src]
+            out[dst] = rows if sign is None else rows * sign[:, None]
+        return out
+
+
 def _concatenate(parts):
     """Reference _canonical_constraint.py:363-438."""
     n_eq = sum(c.n_eq for c in parts)

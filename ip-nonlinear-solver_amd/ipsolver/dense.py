@@ -86,6 +86,51 @@ class DeviceDense:
         return dv.norm(DVec(self.t.reshape(-1)))
 
 
+class AugmentedDense(DeviceDense):
+    """The barrier's augmented Jacobian ``A = [[J_eq, 0], [J_ineq, diag(s)]]`` assembled from a
+    device-mode dense canonical Jacobian (``device_mode.DenseStack``).  Its normal matrix is
+    structured, ``A A' = J J' + diag(0_{m_eq}, s*s)``: ``DenseNormalSolver`` forms the Gram of
+    the first ``n_vars`` columns only and shifts its diagonal (the slacks read off A's diagonal
+    block), and -- the canonical Jacobian being constant (``stack.constant``: linear and box
+    constraints only) -- keeps ``J J'`` for the whole solve in ``stack.gram0``."""
+
+    def __init__(self, t, n_vars, m_eq, stack):
+        DeviceDense.__init__(self, t)
+        self.n_vars, self.m_eq, self.stack = int(n_vars), int(m_eq), stack
+
+
+def augment(J_eq, J_ineq, s, n_vars, n_eq, n_ineq, stack=None):
+    """``[[J_eq, 0], [J_ineq, diag(s)]]`` (tr_interior_point.py:141-194) and its transpose in one
+    launch (csrc/densejac.hip) from row-major device blocks ``J_eq`` / ``J_ineq`` (tensors,
+    leading dimension ``n_vars``).  The transpose becomes the result's cached ``.T``.  With
+    ``stack`` (device-callback mode) the result is an ``AugmentedDense``."""
+    dev = ctx().device
+    m, N = n_eq + n_ineq, n_vars + n_ineq
+    assert J_eq.shape == (n_eq, n_vars) and J_ineq.shape == (n_ineq, n_vars), \
+        (J_eq.shape, J_ineq.shape, n_eq, n_ineq, n_vars)
+    assert len(s) == n_ineq and J_eq.is_contiguous() and J_ineq.is_contiguous()
+    A = torch.empty((m, N), dtype=_F64, device=dev)
+    At = torch.empty((N, m), dtype=_F64, device=dev)
+    _hip.call("ipx_dense_augment", n_eq, n_ineq, n_vars, _p(J_eq) if n_eq else None, n_vars,
+              _p(J_ineq) if n_ineq else None, n_vars, _p(s.t), _p(A), _p(At), stream_ptr())
+    out = DeviceDense(A) if stack is None else AugmentedDense(A, n_vars, n_eq, stack)
+    out._T = DeviceDense(At)
+    out._T._T = out
+    return out
+
+
+def transpose_into(D):
+    """Give a DeviceDense its cached ``.T`` through the augment kernel (no torch transpose)."""
+    m, n = D.shape
+    if D._T is None and m and n:
+        At = torch.empty((n, m), dtype=_F64, device=ctx().device)
+        _hip.call("ipx_dense_augment", m, 0, n, _p(D.t), n, None, n, None, None, _p(At),
+                  stream_ptr())
+        D._T = DeviceDense(At)
+        D._T._T = D
+    return D
+
+
 class DenseNormalSolver:
     """(A A')^-1 through a dense Cholesky: MFMA Gram for a DeviceDense A, sparse
     row products for a DeviceCSR A whose A A' is too wide for the banded
@@ -102,11 +147,10 @@ class DenseNormalSolver:
         G = torch.empty((M, M), dtype=_F64, device=dev)
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         st = stream_ptr()
-        if isinstance(A, DeviceDense):
-            splits = int(lib.ipx_gram_splits(m, n))
-            ws = torch.empty(int(lib.ipx_gram_ws_doubles(m, splits)), dtype=_F64, device=dev) \
-                if splits > 1 else None
-            _hip.call("ipx_gram_f64_mfma_split", m, n, _p(A.t), n, _p(G), _p(ws), splits, st)
+        if isinstance(A, AugmentedDense):
+            self._structured_gram(A, G, st)
+        elif isinstance(A, DeviceDense):
+            _gram(m, n, A.t, n, G, st)
         else:
             p = A.pattern
             _hip.call("ipx_aat_dense", m, _p(p.indptr), _p(p.indices), _p(A.val), _p(G), st)
@@ -133,8 +177,36 @@ class DenseNormalSolver:
         self.Ginv = DeviceDense(X)
         self._pad = torch.zeros(M, dtype=_F64, device=dev) if M != m else None
 
+    @staticmethod
+    def _structured_gram(A, G, st):
+        """G = J J' + diag(0_{m_eq}, s*s) for A = [[J_eq, 0], [J_ineq, diag(s)]]: the Gram of A's
+        first n columns (leading dimension n + m_ineq), then the slack squares on the diagonal
+        -- taken from A itself, so G is a function of A alone.  A constant J keeps its Gram
+        (``A.stack.gram0``) for the whole solve: one shift per refactorization."""
+        m, N = A.shape
+        n = A.n_vars
+        s_ptr = A.t.data_ptr() + 8 * (A.m_eq * N + n)
+        if A.stack.constant:
+            G0 = A.stack.gram0
+            if G0 is None:
+                G0 = A.stack.gram0 = torch.empty_like(G)
+                _gram(m, n, A.t, N, G0, st)
+            _hip.call("ipx_gram_shift", m, A.m_eq, _p(G0), s_ptr, N + 1, _p(G), st)
+        else:
+            _gram(m, n, A.t, N, G, st)
+            _hip.call("ipx_gram_shift", m, A.m_eq, None, s_ptr, N + 1, _p(G), st)
+
     def solve(self, w):
         if self._pad is None:
             return self.Ginv.gemv(w)
         self._pad[:self.m].copy_(w.t)
         return self.Ginv.gemv(DVec(self._pad))[:self.m].copy()
+
+
+def _gram(m, n, A, lda, G, st):
+    """G (padded M x M) = A[:, :n] A[:, :n]' for a row-major A with leading dimension lda."""
+    lib = _hip.load()
+    splits = int(lib.ipx_gram_splits(m, n))
+    ws = torch.empty(int(lib.ipx_gram_ws_doubles(m, splits)), dtype=_F64, device=G.device) \
+        if splits > 1 else None
+    _hip.call("ipx_gram_f64_mfma_split", m, n, _p(A), lda, _p(G), _p(ws), splits, st)

@@ -9,11 +9,11 @@ iterations:
     hess(x) -> DeviceCSR | 1-D tensor (diagonal) | 2-D tensor / DeviceDense (dense) |
                DeviceHessian | None | a tuple of such terms (their sum)
     NonlinearConstraint.fun(x) -> 1-D tensor
-    NonlinearConstraint.jac(x) -> DeviceCSR (a fixed CSRPattern, values refreshed)
+    NonlinearConstraint.jac(x) -> DeviceCSR (a fixed CSRPattern, values refreshed) |
+                                  2-D CUDA tensor / DeviceDense (dense), any ``kind``
     NonlinearConstraint.hess(x, v) -> DeviceCSR | 1-D tensor (diagonal) | None
-    LinearConstraint(A)  with A a scipy sparse matrix, a DeviceCSR, or -- dense Jacobian,
-                         BASELINE config 2: every row an equality -- a 2-D CUDA tensor /
-                         DeviceDense
+    LinearConstraint(A)  with A a scipy sparse matrix, a DeviceCSR, or a 2-D CUDA tensor /
+                         DeviceDense (dense), any ``kind``
     BoxConstraint(kind)  unchanged
 
 Order of evaluations: with the device chains of the outer iteration (sqp.ChainStages) ``fun``
@@ -31,6 +31,15 @@ are value refreshes on patterns built once: gather / scatter kernels over
 index maps computed on the host at initialisation (symbolic work only).
 Finite-difference Hessians are not available in this mode (they evaluate host
 callbacks by construction).
+
+Dense Jacobians: a single constraint whose rows are all equalities in the caller's order passes
+its matrix through untouched (BASELINE config 2).  Any other list with a dense part -- inequality
+rows, equalities out of order, several constraints, sparse or box parts next to the dense one --
+is written into ONE dense buffer ``[J_ineq; J_eq]`` per Jacobian evaluation (``DenseStack``:
+row gathers with sign, CSR rows densified; the tables from ``canonical.DenseRowPlan``), whose
+row slices the outer loops see; the barrier's augmented Jacobian and its transpose are then one
+kernel (``dense.augment``) and its normal matrix ``J J' + diag(0, s*s)`` (``dense.AugmentedDense``).
+Densified sparse / box rows are capped at ``DenseNormalSolver.MAX_ROWS_FROM_SPARSE``.
 """
 import numpy as np
 import scipy.sparse as sps
@@ -156,13 +165,19 @@ class DeviceRowMap:
             else DVec.zeros(0)
         return c_ineq, c_eq
 
+    @property
+    def passes_dense_through(self):
+        """Rows all equalities, in the caller's order: a dense Jacobian IS the canonical one."""
+        return self.n_ineq == 0 and np.array_equal(self.eq, np.arange(self.fun_len))
+
     def jac(self, J):
         from .dense import DeviceDense
         if isinstance(J, DeviceDense):
-            # a dense Jacobian passes through whole: rows all equalities, in order
-            if self.n_ineq or not np.array_equal(self.eq, np.arange(J.shape[0])):
-                raise NotImplementedError("device-callback mode: a dense constraint Jacobian "
-                                          "must consist of equality rows only (kind 'equals')")
+            # a dense Jacobian passes through whole: rows all equalities, in order (any other
+            # dense case is stacked by DeviceCanonical -- DenseStack -- and never gets here)
+            if not self.passes_dense_through:
+                raise NotImplementedError("device-callback mode: a constraint Jacobian that was "
+                                          "sparse at x0 became dense")
             return self._no_rows(J.shape[1]), J
         if self.all_eq:
             return self._no_rows(J.shape[1]), J
@@ -309,14 +324,14 @@ class _DeviceConstraint:
 
 
 def _check_jac(J):
-    """What a device-mode ``jac`` callback may return: a DeviceCSR, or -- dense Jacobians,
-    equality rows only (``DeviceRowMap.jac``) -- a DeviceDense / a 2-D CUDA tensor."""
+    """What a device-mode ``jac`` callback may return: a DeviceCSR, or a dense Jacobian (any
+    ``kind``) as a DeviceDense / a 2-D CUDA tensor."""
     from .dense import DeviceDense
     if torch.is_tensor(J) and J.dim() == 2 and J.is_cuda:
         J = DeviceDense(J.to(_F64).contiguous())
     if not isinstance(J, (DeviceCSR, DeviceDense)):
         raise TypeError("device-callback mode: `jac` must return an ipsolver.device.DeviceCSR "
-                        "(or, for a dense Jacobian of equality rows, a 2-D CUDA tensor)")
+                        "(or, for a dense Jacobian, a 2-D CUDA tensor / DeviceDense)")
     return J
 
 
@@ -366,11 +381,19 @@ class DeviceCanonical:
         self._empty = DeviceRowMap._no_rows(self.n_vars)
         vals = [p.rows.values(p.f0) for p in self.parts]
         self.c_ineq0, self.c_eq0 = self._stack_values(vals)
-        self.J_ineq0, self.J_eq0 = self._stack_jacs([p.rows.jac(p.J0) for p in self.parts])
-        self.hess = self._hess if any(p.hess is not None for p in self.parts) else None
         # linear / box constraints only: jac(x) is the same pair of matrices for every x
         # (canonical.CanonicalConstraint.constant_jac)
         self.constant_jac = all(p.constant_jac for p in self.parts)
+        from .dense import DeviceDense
+        dense = [isinstance(p.J0, DeviceDense) for p in self.parts]
+        single_pass = len(self.parts) == 1 and self.parts[0].rows.passes_dense_through
+        self.dense_stack = DenseStack(self.parts, self.n_vars, self.constant_jac) \
+            if any(dense) and not single_pass else None
+        if self.dense_stack is not None:
+            self.J_ineq0, self.J_eq0 = self.dense_stack.assemble([p.J0 for p in self.parts])
+        else:
+            self.J_ineq0, self.J_eq0 = self._stack_jacs([p.rows.jac(p.J0) for p in self.parts])
+        self.hess = self._hess if any(p.hess is not None for p in self.parts) else None
 
     def _stack_values(self, pairs):
         ineq = [a for a, _ in pairs if len(a)]
@@ -390,6 +413,8 @@ class DeviceCanonical:
     def jac(self, x):
         if self.constant_jac:
             return self.J_ineq0, self.J_eq0
+        if self.dense_stack is not None:
+            return self.dense_stack.assemble([p.jac(x) for p in self.parts])
         return self._stack_jacs([p.rows.jac(p.jac(x)) for p in self.parts])
 
     def _hess(self, x, v_eq, v_ineq):
@@ -401,6 +426,62 @@ class DeviceCanonical:
             i_eq += p.n_eq
             i_ineq += p.n_ineq
         return terms
+
+
+class DenseStack:
+    """The canonical Jacobian of a constraint list with a dense part, as ONE dense device
+    buffer ``[J_ineq; J_eq]`` (reference: ``_RowMap.dense_jac`` + ``_stack_dense``).  The row
+    tables (``canonical.DenseRowPlan``) are built once; every evaluation is one launch per part
+    into a fresh buffer -- a row gather with sign for a dense part, the densified rows of a CSR
+    part -- and ``J_ineq`` / ``J_eq`` are contiguous row slices of it that carry ``stack``
+    (``backend_hip.augmented_jacobian`` builds an ``AugmentedDense`` from them)."""
+
+    def __init__(self, parts, n_vars, constant):
+        from .canonical import DenseRowPlan
+        from .dense import DeviceDense, DenseNormalSolver
+        plan = DenseRowPlan([(p.rows.eq, p.rows.ineq, p.rows.sign_h) for p in parts])
+        densified = sum(len(src) for p, (src, _, _) in zip(parts, plan.parts)
+                        if not isinstance(p.J0, DeviceDense))
+        if densified > DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
+            raise NotImplementedError(
+                "device-callback mode: a dense constraint Jacobian next to sparse or box "
+                "constraints densifies their rows; %d such rows exceed the limit of %d "
+                "(DenseNormalSolver.MAX_ROWS_FROM_SPARSE) -- give every constraint a sparse "
+                "Jacobian (DeviceCSR) instead" % (densified, DenseNormalSolver.MAX_ROWS_FROM_SPARSE))
+        self.m_ineq, self.m_eq, self.n_vars = plan.m_ineq, plan.m_eq, n_vars
+        self.constant = bool(constant)
+        self.gram0 = None          # J J' of a constant J (dense.DenseNormalSolver)
+        self.tables = [(len(src), _idx(src), None if sign is None else _vec(sign), _idx(dst),
+                        p.rows.fun_len) for p, (src, sign, dst) in zip(parts, plan.parts)]
+
+    def assemble(self, jacs):
+        from .dense import DeviceDense
+        m, n = self.m_ineq + self.m_eq, self.n_vars
+        if m == 0:
+            empty = DeviceRowMap._no_rows(n)
+            return empty, empty
+        buf = torch.empty((m, n), dtype=_F64, device=ctx().device)
+        st = stream_ptr()
+        for J, (rows, src, sign, dst, fun_len) in zip(jacs, self.tables):
+            if tuple(J.shape) != (fun_len, n):
+                raise ValueError("device-callback mode: a constraint Jacobian of shape %r, "
+                                 "expected %r" % (tuple(J.shape), (fun_len, n)))
+            if rows == 0:
+                continue
+            if isinstance(J, DeviceDense):
+                _hip.call("ipx_dense_gather_rows", rows, n, _p(J.t), n, _p(src), _p(sign),
+                          _p(dst), _p(buf), n, 0, st)
+            else:
+                pat = J.pattern
+                _hip.call("ipx_csr_rows_to_dense", rows, n, _p(pat.indptr), _p(pat.indices),
+                          _p(J.val), _p(src), _p(sign), _p(dst), _p(buf), n, st)
+        J_ineq, J_eq = DeviceDense(buf[:self.m_ineq]), DeviceDense(buf[self.m_ineq:])
+        if self.m_ineq == 0:
+            # equality rows only: the SQP's matrix, its transpose made by the augment kernel
+            from .dense import transpose_into
+            transpose_into(J_eq)
+        J_ineq.stack = J_eq.stack = self
+        return J_ineq, J_eq
 
 
 def _as_terms(h):

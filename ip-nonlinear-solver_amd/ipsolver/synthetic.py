@@ -139,6 +139,19 @@ class CenteredDenseNLP:
         return ns.NonlinearConstraint(self.constr_fun, kind, self.constr_jac, self.constr_hess)
 
 
+def mixed_interval_kind(m, seed=0, width=0.05):
+    """``('interval', lb, ub)`` over ``m`` rows of ``CenteredDenseNLP``'s constraint with every
+    kind of canonical row, interleaved by a seeded permutation: a third equalities
+    (``lb == ub == 0``), a third one-sided ``(-inf, width]``, a third two-sided
+    ``[-width, width]`` (one canonical row per finite bound)."""
+    perm = np.random.default_rng(seed + 777).permutation(m)
+    k = m // 3
+    lb, ub = np.zeros(m), np.zeros(m)
+    lb[perm[k:2 * k]], ub[perm[k:2 * k]] = -np.inf, width
+    lb[perm[2 * k:]], ub[perm[2 * k:]] = -width, width
+    return ("interval", lb, ub)
+
+
 class DenseDeviceCallbacks:
     """``CenteredDenseNLP`` with every callback on the GPU (device-callback mode: 2-D CUDA
     tensors for the Jacobian and the Hessian; user-land code, torch freely)."""
