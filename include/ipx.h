@@ -360,6 +360,19 @@ typedef struct ipx_cg_args {
   void *R_ll;
   int64_t R_hw;
   int64_t *R_seq;
+  /* A low-rank term of the Hessian (csrc/lowrank.hip: B = sigma I + W C W' on the first LR_rows
+   * rows, zero elsewhere), added by every H.p of the loop behind the CSR / dense / diagonal part
+   * -- or alone, H_rowptr and H_val NULL: then H_diag (or nothing) is the rest.  LR_W = the
+   * ring buffer (2 LR_mem columns of LR_rows), LR_state = its state block, LR_part =
+   * 2 LR_mem x ipx_lowrank_grid(LR_rows) doubles of scratch.  With LR_W set, the p'Hp partials
+   * of the final Hp are per workgroup of that product (part1_count: ipx_lowrank_grid(LR_rows),
+   * part1 2 x that long); the resident and PEER forms and the outer-iteration chains refuse
+   * the block.  LR_W NULL: every launch sequence is unchanged. */
+  const double *LR_W;
+  const double *LR_state;
+  double *LR_part;
+  int64_t LR_mem;
+  int64_t LR_rows;
 } ipx_cg_args;
 int ipx_cg_resident_ok(const ipx_cg_args *a);
 int64_t ipx_cg_resident_ll_words(int32_t nwg, int32_t hw);
@@ -729,6 +742,37 @@ void ipx_sqp_radius_host(double *q);
 /* box_sphere_intersections' scalar tail (qp_subproblem.py:99-149,194-234,286-296) from the seven
  * sums of ipx_box_sphere_reduce: out3 = (ta, tb, intersect) */
 void ipx_sqp_box_sphere_host(const double *sums7, double radius, int entire_line, double *out3);
+
+/* ---- limited-memory quasi-Newton Hessians (csrc/lowrank.hip, ipsolver/quasi_newton.py) ----
+ * B = sigma I + W C W' with W = [S Y]: two rings of `mem` columns (column j at W + j n; slot t
+ * holds s_t in column t and y_t in column mem + t; unwritten columns zero), C (2 mem)^2 doubles.
+ * State block (ipx_lowrank_state_doubles, zero but for [0] = the initial sigma):
+ *   [0] sigma, [1] stored pairs, [2] next slot, [3] updates, [4] skipped, [5] sigma fixed,
+ *   [6] the last update stored its pair, [7] that slot, [IPX_LR_HDR...] the Gram W'W, then C
+ *   (both 2 mem x 2 mem, row major).
+ * kind 0: L-BFGS (Byrd, Nocedal & Schnabel 1994 compact form; stored when s'y > threshold
+ * ||s|| ||y||), kind 1: L-SR1 (stored when |s'(y - Bs)| >= threshold ||s|| ||y - Bs|| and the
+ * middle matrix inverts with every pivot above 1e-14 max|entry|).  init_scale <= 0: sigma from
+ * the pairs ('auto'). */
+#define IPX_LR_MAX_MEMORY 32
+#define IPX_LR_HDR 16
+int64_t ipx_lowrank_state_doubles(int32_t mem);
+/* workgroups of the update's and the product's partial sums, and the scratch they need */
+int ipx_lowrank_grid(int64_t n);
+int64_t ipx_lowrank_part_doubles(int64_t n, int32_t mem);
+/* one update with the pair (s, y): s'W, y'W, s's, s'y, y'y in one multi-dot kernel, the skip
+ * rule + middle matrix + C in one single-workgroup kernel, s and y copied into their slot when
+ * stored; s's == 0 changes nothing (not counted).  Three launches, no read-back. */
+int ipx_lowrank_update(int32_t kind, int64_t n, int32_t mem, double init_scale, double threshold,
+                       double *W, const double *s, const double *y, double *state, double *part,
+                       void *stream);
+/* out = sigma p + W C W'p (accumulate != 0: added to out); two launches, out != p */
+int ipx_lowrank_apply(int64_t n, int32_t mem, const double *W, const double *state, const double *p,
+                      double *out, int32_t accumulate, double *part, void *stream);
+/* the update's middle-matrix step on a HOST state block from the folded sums
+ * dots = (s'W [2 mem], y'W [2 mem], s's, s'y, y'y): the same arithmetic as the kernel */
+void ipx_lowrank_middle_host(int32_t kind, int32_t mem, double init_scale, double threshold,
+                             double *state, const double *dots);
 
 #ifdef __cplusplus
 }

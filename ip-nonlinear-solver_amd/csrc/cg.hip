@@ -1070,9 +1070,12 @@ static bool fused_hp(const ipx_cg_args *a) {
 // Unfused H.p; when the fused step2+H.p kernel is in use it also saves the tile
 // boundaries of the p it was given (that kernel's halo source).
 static bool dense_loop(const ipx_cg_args *a) { return a->solver_kind == 2; }
+// a low-rank term rides behind every H.p (csrc/lowrank.hip)
+static bool lowrank_on(const ipx_cg_args *a) { return a->LR_W != nullptr && !a->H_operator; }
 // entries per half of part1: row tiles of a CSR Hessian / workgroups of the dense matvec
 static int part1_count(const ipx_cg_args *a) {
   if (a->H_operator) return 1;                   // [unused, p'Hp] written by the caller
+  if (lowrank_on(a)) return ipx_lowrank_grid(a->LR_rows);   // the low-rank product's workgroups
   if (dense_loop(a) && !a->H_rowptr) {
     const int g = (int)((a->n + 3) / 4);
     return g > 2048 ? 2048 : g;
@@ -1080,15 +1083,26 @@ static int part1_count(const ipx_cg_args *a) {
   return (int)a->H_ntiles;
 }
 
+// the low-rank term behind an H.p that left Hp (has_base) or none (H is that term + diagonal)
+static int launch_lowrank(const ipx_cg_args *a, bool has_base, const double *guard, hipStream_t st) {
+  return ipx_lowrank_cg_launch(a->n, a->LR_rows, (int)a->LR_mem, a->LR_W, a->LR_state, a->LR_part,
+                               a->p, a->Hp, a->H_diag, has_base ? 1 : 0, a->part1, guard, st);
+}
+
 static int launch_hp(const ipx_cg_args *a, const double *guard, hipStream_t st) {
   if (a->H_operator) return IPX_OK;              // the caller applies H between the iterations
+  if (lowrank_on(a) && !a->H_rowptr && !a->H_val)
+    return launch_lowrank(a, false, guard, st);  // H = low-rank term (+ diagonal)
   if (dense_loop(a) && !a->H_rowptr) {           // dense Hessian (row major n x n in H_val)
     int np = 0;
-    return ipx_dense_gemv_launch((int)a->n, (int)a->n, a->H_val, a->n, a->p, 1.0, a->H_diag, 0.0,
-                                 nullptr, a->Hp, a->part1, &np, guard, st);
+    int rc = ipx_dense_gemv_launch((int)a->n, (int)a->n, a->H_val, a->n, a->p, 1.0, a->H_diag, 0.0,
+                                   nullptr, a->Hp, a->part1, &np, guard, st);
+    if (rc || !lowrank_on(a)) return rc;
+    return launch_lowrank(a, true, guard, st);
   }
   ipx_csr_view H{(int)a->n, (int)a->n, a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles, (int)a->H_ntiles};
   int rc = ipx_spmv_launch(H, a->p, 1.0, a->H_diag, 0.0, nullptr, a->Hp, a->part1, guard, st);
+  if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, guard, st);
   if (rc || !fused_hp(a)) return rc;
   const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
   hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0, st,
@@ -1416,7 +1430,7 @@ int ipx_cg_shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
 static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t phase,
                           int32_t it, int32_t mode, void *stream, bool fuse_comm) {
   if (!a || !e || phase < 0 || phase > 1 || !e->s1 || !e->pack || a->solver_kind > 1 ||
-      e->nseg < 1 || e->nseg > 4)
+      e->nseg < 1 || e->nseg > 4 || a->LR_W)
     return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (fuse_comm) {
@@ -1574,7 +1588,7 @@ static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
 // themselves -- no collective call, no host between the iterations.
 int ipx_cg_shard2_iterate(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t it_begin,
                           int32_t it_end, void *stream) {
-  if (!a || !e || !e->peer || it_end < it_begin) return IPX_EINVAL;
+  if (!a || !e || !e->peer || it_end < it_begin || a->LR_W) return IPX_EINVAL;
   // e->fuse_comm is the GROUP's decision (ipx_cg_shard2_fusable on every rank, the minimum
   // taken over the ranks by the caller): the two forms order the collectives of an iteration
   // differently, so a rank may not pick one from its own slice of the matrices
@@ -1592,7 +1606,7 @@ int ipx_cg_shard2_iterate(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
 // The batch as one resident launch per rank (csrc/resident.hip, PEER form).
 int ipx_cg_shard2_resident(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t it_begin,
                            int32_t it_end, void *stream) {
-  if (!a || !e) return IPX_EINVAL;
+  if (!a || !e || a->LR_W) return IPX_EINVAL;
   return ipx_cg_shard2_resident_launch(a, e, it_begin, it_end, part1_count(a), (hipStream_t)stream);
 }
 
@@ -1613,7 +1627,7 @@ int ipx_cg_save_pb(const ipx_cg_args *a, void *stream) {
 // slice of A and H).  The ranks must agree before anyone sets e->fuse_comm: the caller
 // reduces this value with MIN over the group (ipsolver/sharded.py FusedShardedCG).
 int ipx_cg_shard2_fusable(const ipx_cg_args *a, const ipx_shard2_ext *e) {
-  if (!a || !e || !e->peer) return 0;
+  if (!a || !e || !e->peer || a->LR_W) return 0;
   ipx_shard2_ext asked = *e;
   asked.fuse_comm = 1;
   return peer_fusable(a, &asked) ? 1 : 0;
@@ -1621,7 +1635,7 @@ int ipx_cg_shard2_fusable(const ipx_cg_args *a, const ipx_shard2_ext *e) {
 
 // The own-range sum of the p'Hp partials on its own (priming the sharded loop).
 int ipx_cg_shard2_fold_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, void *stream) {
-  if (!a || !e || !e->s1 || e->nseg < 1 || e->nseg > 4) return IPX_EINVAL;
+  if (!a || !e || !e->s1 || e->nseg < 1 || e->nseg > 4 || a->LR_W) return IPX_EINVAL;
   return pack_hp(a, e, (hipStream_t)stream);
 }
 
@@ -1970,7 +1984,7 @@ int ipx_cg_prime_dev(const ipx_cg_args *a, const int32_t *A_tiles, int32_t A_nti
                      int steps, const double *c_part, int32_t c_npart, int x_is_zero,
                      hipStream_t stream) {
   if (!a || !c || !red || !ws || !A_tiles || a->solver_kind > 1 || a->m <= 0 || a->H_operator ||
-      !a->H_rowptr || !a->t || first_end < 0)
+      !a->H_rowptr || !a->t || first_end < 0 || a->LR_W)   // (H x0 would miss a low-rank term)
     return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const ipx_csr_view A{(int)a->m, (int)a->n, a->A_rowptr, a->A_colidx, a->A_val, A_tiles, A_ntiles};
@@ -2062,7 +2076,9 @@ int ipx_cg_step2_hp(const ipx_cg_args *a, int32_t it, int32_t mode, void *stream
   if (!(mode & 2)) cmp.add(p4, np4, 1, 1024);
   int rc = cmp.launch(nullptr, st);
   if (rc) return rc;
-  return launch_step2_hp(a, it, mode, p2, np2, p3, np3, p4, np4, st);
+  rc = launch_step2_hp(a, it, mode, p2, np2, p3, np3, p4, np4, st);
+  if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, a->state + ST_STOP, st);
+  return rc;
 }
 
 // Tail of an iteration after the host handled a stop-5 / stop-6 event:
@@ -2200,7 +2216,7 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
     const double *r_in = fuse1 ? a->r_next : a->r;      // what the r - A'v SpMV reads
     Compactor cmp(a);
     const double *p1 = a->part1;
-    int np1 = (int)a->H_ntiles;
+    int np1 = part1_count(a);
     cmp.add(p1, np1, 2, 2048);      // beyond what a consumer folds in one or two rounds
     // trust radius +inf, no box (fused step1 implies no box): the radius / box tests of
     // qp_subproblem.py:583,599 cannot trigger; their sums are neither formed nor folded
@@ -2285,6 +2301,7 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
       MARK(6);
       rc = launch_step2_hp(a, it, (a->m > 0 ? 0 : 2) | (no_xn2 ? 1 : 0), p2, np2,
                            p3, np3, p4, n4, st, a->r);
+      if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, guard, st);
     } else {
       hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
                          a->state, it & 1, (a->m > 0 ? 0 : 2) | (no_xn2 ? 1 : 0), p2, np2, p3, np3,

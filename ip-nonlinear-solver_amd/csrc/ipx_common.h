@@ -24,6 +24,14 @@ int ipx_read_begin(unsigned int **pinned_out, unsigned int *tag_out);
 int ipx_read_wait(unsigned int *pinned, unsigned int tag, int k, double *host_out, hipStream_t st);
 int ipx_read_ints(const int *dev, int k, int *host_out, hipStream_t st);
 
+// The low-rank Hessian term of the CG loop (csrc/lowrank.hip): Hp <- base + sigma p + W C W'p on
+// the first `rows` rows (base = Hp as the H.p before it left it, or diag * p / 0 when has_base is
+// 0), p'Hp partials of the final Hp into part1[G + b] (part1[b] = 0), G = ipx_lowrank_grid(rows);
+// two launches behind `guard` (the loop's stop word).
+int ipx_lowrank_cg_launch(int64_t n, int64_t rows, int mem, const double *W, const double *state,
+                          double *part, const double *p, double *Hp, const double *diag,
+                          int has_base, double *part1, const double *guard, hipStream_t st);
+
 // kernel launches of the library since it was loaded (ipx_launch_count; misc.hip): counted where
 // every launch is checked
 extern long long g_ipx_launches;

@@ -1056,7 +1056,7 @@ void res_launch(const ResJob &J, size_t lds, hipStream_t st) {
 // 1 when the argument block can run the resident form (sizes within the kernel's budgets, one
 // compute unit per workgroup on this device)
 extern "C" int ipx_cg_resident_ok(const ipx_cg_args *a) {
-  if (!a || !a->resident || !a->R_ll || !a->R_seq) return 0;
+  if (!a || !a->resident || !a->R_ll || !a->R_seq || a->LR_W) return 0;   // (no low-rank term)
   ipx_pcr_view pv;
   if (!ipx_banded_pcr_view(a->banded, &pv)) return 0;
   return res_tables_ok(a, pv, pv.nwg) ? 1 : 0;
@@ -1097,7 +1097,7 @@ int ipx_cg_resident_launch(const ipx_cg_args *a, int32_t it_begin, int32_t it_en
 // ipx_cg_shard2_resident_ok, minimum over the ranks): a rank on another form would leave the
 // others waiting for its records.
 extern "C" int ipx_cg_shard2_resident_ok(const ipx_cg_args *a, const ipx_shard2_ext *e) {
-  if (!a || !e || !e->peer || e->nseg != 1 || e->res_nwg < 1) return 0;
+  if (!a || !e || !e->peer || e->nseg != 1 || e->res_nwg < 1 || a->LR_W) return 0;
   const ipx_peer *peer = (const ipx_peer *)e->peer;
   ipx_pcr_view pv;
   if (!ipx_banded_pcr_view(a->banded, &pv)) return 0;

@@ -935,6 +935,7 @@ int ipx_sqp_front(const ipx_sqp_args *s, int have_dn, int with_dogleg, int with_
                   double box_factor, double tol_in, double norm_A, int32_t first_end,
                   void *stream) {
   if (!s || !s->cg || !s->q || !s->part || !s->dn || !s->ct || s->m <= 0) return IPX_EINVAL;
+  if (s->cg->LR_W) return IPX_EINVAL;      // (the chains have no low-rank Hessian term)
   if (with_dogleg && (!s->d || !s->Hd || !s->Ad)) return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const ipx_cg_args *a = s->cg;

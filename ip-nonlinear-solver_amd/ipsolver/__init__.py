@@ -8,6 +8,7 @@ loudly when the library or a HIP device is missing.
 """
 from .minimize import minimize_constrained
 from .constraints import NonlinearConstraint, LinearConstraint, BoxConstraint
+from .quasi_newton import LBFGS, LSR1
 
 __all__ = ['minimize_constrained', 'NonlinearConstraint', 'LinearConstraint',
-           'BoxConstraint']
+           'BoxConstraint', 'LBFGS', 'LSR1']

@@ -124,6 +124,9 @@ _SIGNATURES = {
     "ipx_sqp_judge": [_P, _P, _F64, _P, _P],
     "ipx_sqp_refresh": [_P, _P],
     "ipx_sqp_cg_timing": [_c.c_int, _P, _P],
+    "ipx_lowrank_grid": [_I64],
+    "ipx_lowrank_update": [_I32, _I64, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P],
+    "ipx_lowrank_apply": [_I64, _I32, _P, _P, _P, _P, _I32, _P, _P],
 }
 _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_launch_count": _c.c_longlong, "ipx_read_count": _c.c_longlong,
@@ -133,7 +136,9 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_cg_resident_ll_words": _I64, "ipx_cg_prime_ws_doubles": _I64,
              "ipx_peer_resident_launches": _I64, "ipx_cg_resident_limits": None,
              "ipx_sqp_part_doubles": _I64, "ipx_sqp_model_host": None, "ipx_sqp_ratio_host": None,
-             "ipx_sqp_radius_host": None, "ipx_sqp_box_sphere_host": None}
+             "ipx_sqp_radius_host": None, "ipx_sqp_box_sphere_host": None,
+             "ipx_lowrank_state_doubles": _I64, "ipx_lowrank_part_doubles": _I64,
+             "ipx_lowrank_middle_host": None}
 _EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
                    "ipx_dense_padded": [_I64], "ipx_gram_ws_doubles": [_I64, _I32],
                    "ipx_peer_create": [_I32, _I32, _I64],
@@ -142,7 +147,9 @@ _EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy"
                    "ipx_cg_prime_ws_doubles": [_P, _I32], "ipx_peer_resident_launches": [_P],
                    "ipx_cg_resident_limits": [_P], "ipx_sqp_part_doubles": [_P],
                    "ipx_sqp_model_host": [_P], "ipx_sqp_ratio_host": [_P],
-                   "ipx_sqp_radius_host": [_P], "ipx_sqp_box_sphere_host": [_P, _F64, _c.c_int, _P]}
+                   "ipx_sqp_radius_host": [_P], "ipx_sqp_box_sphere_host": [_P, _F64, _c.c_int, _P],
+                   "ipx_lowrank_state_doubles": [_I32], "ipx_lowrank_part_doubles": [_I64, _I32],
+                   "ipx_lowrank_middle_host": [_I32, _I32, _F64, _F64, _P, _P]}
 
 _lib = None
 
@@ -202,8 +209,10 @@ def load():
 # and the 16-bit index tables / the merged diagonal are what every qualifying pattern gets)
 #   no-step-chain      the outer iteration's stages host-driven (sqp.HostStages) instead of as
 #                      device chains (csrc/sqp.hip)
+#   no-lowrank-loop    a quasi-Newton Hessian term applied by the host between the CG loop's
+#                      iterations (the operator form) instead of inside its launches
 DEBUG_FORMS = ("no-fuse", "no-resident", "no-compact-groups", "no-affine-groups", "keep-xn2",
-               "pack-comm", "no-post-tail", "no-step-chain")
+               "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop")
 
 
 def debug_form(name):

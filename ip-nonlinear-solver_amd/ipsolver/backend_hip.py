@@ -277,9 +277,12 @@ def hessian_operator(terms, n_vars, slack_block):
     block: ``[Hx p_x ; slack_block * p_s]`` (tr_interior_point.py:222-241)."""
     flat = terms.flat_terms() if isinstance(terms, HessianSum) else list(terms)
     n_total = n_vars + (len(slack_block) if slack_block is not None else 0)
-    csr, diag, others = None, None, []
+    csr, diag, others, lowrank = None, None, [], None
     sparse_terms = []
     for h in flat:
+        if getattr(h, "lowrank_term", False) and lowrank is None:
+            lowrank = h                 # (quasi-Newton objective: the device loop applies it)
+            continue
         if sps.issparse(h):
             h = sps.csr_matrix(h)
             if not h.has_canonical_format:
@@ -314,7 +317,7 @@ def hessian_operator(terms, n_vars, slack_block):
             others.append(up)
     if slack_block is None:
         return DeviceHessian(n_vars, csr, diag, others,
-                             merge=_cg_length["last"] >= MERGE_DIAGONAL_FROM)
+                             merge=_cg_length["last"] >= MERGE_DIAGONAL_FROM, lowrank=lowrank)
     # z-space: extend the CSR block with empty slack rows, put the slack block
     # on the diagonal, pad any other x-space term
     if csr is not None:
@@ -322,7 +325,7 @@ def hessian_operator(terms, n_vars, slack_block):
     xdiag = diag if diag is not None else DVec.zeros(n_vars)
     zdiag = dv.hstack((xdiag, slack_block))
     return DeviceHessian(n_total, csr, zdiag,
-                         [PaddedOperator(h, n_vars, n_total) for h in others])
+                         [PaddedOperator(h, n_vars, n_total) for h in others], lowrank=lowrank)
 
 
 def augmented_jacobian(J_eq, J_ineq, s, n_vars, n_eq, n_ineq):

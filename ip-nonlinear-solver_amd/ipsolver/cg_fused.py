@@ -45,7 +45,8 @@ class CgArgs(ctypes.Structure):
         ("H_col16", _P), ("H_rowlen", _P), ("A_col16", _P), ("no_radius", _I64),
         ("A_off16", _P), ("A_rowfirst", _P), ("A_rl", _I64), ("P_win", _P), ("P_nspan", _I64),
         ("P_navn", _I64), ("H_operator", _I64),
-        ("resident", _I64), ("R_ll", _P), ("R_hw", _I64), ("R_seq", _P))]
+        ("resident", _I64), ("R_ll", _P), ("R_hw", _I64), ("R_seq", _P),
+        ("LR_W", _P), ("LR_state", _P), ("LR_part", _P), ("LR_mem", _I64), ("LR_rows", _I64))]
 
 
 # Counters over the life of the process (diagnostics: how often the device loop
@@ -60,12 +61,38 @@ STATS = {"calls": 0, "iterations": 0, "batches": 0, "box_events": 0, "refine_eve
 
 
 def _hessian_parts(H):
-    """(csr, diag) for the Hessian operator types the fused loop understands."""
+    """(csr, diag) for the Hessian operator types the fused loop understands (without a
+    low-rank term: every other consumer of these parts -- the outer iteration's chains, the
+    row-sharded loop -- has none)."""
     from .operators import DeviceHessian
     if isinstance(H, DeviceCSR) and H.shape[0] == H.shape[1]:
         return H, None
-    if isinstance(H, DeviceHessian) and H.csr is not None and not H.others:
+    if isinstance(H, DeviceHessian) and H.csr is not None and not H.others \
+            and H.lowrank is None:
         return H.csr, H.diag
+    return None
+
+
+def _lowrank_part(H):
+    """The low-rank term the loop applies inside its launches (ipx_cg_args.LR_*), or None:
+    none, other terms beside it that only the host applies, or the debug form
+    ``no-lowrank-loop`` (then the whole Hessian is an operator)."""
+    from .operators import DeviceHessian
+    if not isinstance(H, DeviceHessian) or H.lowrank is None or H.others \
+            or _hip.debug_form("no-lowrank-loop"):
+        return None
+    return H.lowrank
+
+
+def _loop_parts(H):
+    """(csr, diag, lowrank) of a Hessian the separate launches of the loop apply themselves:
+    CSR (+ diagonal), or a low-rank term with an optional CSR and diagonal; else None."""
+    parts = _hessian_parts(H)
+    if parts is not None:
+        return parts[0], parts[1], None
+    lr = _lowrank_part(H)
+    if lr is not None:
+        return H.csr, H.diag, lr
     return None
 
 
@@ -77,7 +104,8 @@ def _dense_hessian(H):
     if isinstance(H, DeviceDense) and H.shape[0] == H.shape[1]:
         return H
     if isinstance(H, DeviceHessian) and H.csr is None and H.diag is None \
-            and len(H.others) == 1 and isinstance(H.others[0], DeviceDense):
+            and len(H.others) == 1 and isinstance(H.others[0], DeviceDense) \
+            and H.lowrank is None:
         return H.others[0]
     return None
 
@@ -390,7 +418,7 @@ def supports(H, Z, Y):
     if isinstance(P.A, DeviceDense):          # dense Jacobian (config 2): dense or CSR Hessian
         return (P.m > 0 and isinstance(P.solver, DenseNormalSolver)
                 and not getattr(P.solver, "refine_steps", 0)
-                and (_dense_hessian(H) is not None or _hessian_parts(H) is not None))
+                and (_dense_hessian(H) is not None or _loop_parts(H) is not None))
     if not isinstance(P.A, DeviceCSR):
         return False
     if P.m == 0 or _solver_kind(P.solver) is None:
@@ -399,7 +427,7 @@ def supports(H, Z, Y):
     # ``dot`` over device vectors (finite differences, user callbacks, dense or padded terms:
     # _canonical_constraint.py:119-139) is applied between two iterations, the scalar branches
     # stay on the device all the same
-    return _hessian_parts(H) is not None or hasattr(H, "dot")
+    return _loop_parts(H) is not None or hasattr(H, "dot")
 
 
 def _ptr(t):
@@ -417,12 +445,14 @@ def _signature(H, P, lb, ub):
     from .dense import DeviceDense
     if isinstance(P.A, DeviceDense):
         return None
-    if _hessian_parts(H) is None:
+    parts = _loop_parts(H)
+    if parts is None:
         return None                      # operator Hessians: not pooled
-    Hc, Hd = _hessian_parts(H)
+    Hc, Hd, LR = parts
     flags = os.environ.get("IPX_DEBUG_FORMS", "")
-    return (id(Hc.pattern), Hd is None, id(P.A.pattern), lb is None, ub is None,
-            _solver_kind(P.solver), int(getattr(P.solver, "k", 0)), flags)
+    return (id(Hc.pattern) if Hc is not None else None, Hd is None, id(P.A.pattern), lb is None,
+            ub is None, _solver_kind(P.solver), int(getattr(P.solver, "k", 0)), flags,
+            id(LR.mem) if LR is not None else None)
 
 
 def _loop_for(H, P, lb, ub):
@@ -464,7 +494,7 @@ class _Loop:
         a = self.args
         A = P.A
         At = A.T
-        Hc, Hd = _hessian_parts(H)
+        Hc, Hd, LR = _loop_parts(H)
         if a.solver_kind == 0:
             geo = (ctypes.c_int32 * 2)()
             ok = bool(lib.ipx_banded_decoupled_geometry(ctypes.c_void_p(P.solver.handle), geo))
@@ -476,8 +506,11 @@ class _Loop:
             a.banded = ctypes.c_void_p(P.solver.handle)
         else:
             a.banded = ctypes.cast(ctypes.pointer(P.solver.c_args()), ctypes.c_void_p)
-        a.A_val, a.At_val, a.H_val = _ptr(A.val), _ptr(At.val), _ptr(Hc.val)
+        a.A_val, a.At_val = _ptr(A.val), _ptr(At.val)
+        a.H_val = _ptr(Hc.val) if Hc is not None else None
         a.H_diag = _ptr(Hd.t) if Hd is not None else None
+        self.lowrank = LR
+        self._bind_lowrank(LR)
         a.lb = _ptr(lb.t) if lb is not None else None
         a.ub = _ptr(ub.t) if ub is not None else None
         if a.At_ell_val:
@@ -486,8 +519,27 @@ class _Loop:
         a.no_radius = 0
         self.x = torch.empty(self.n, dtype=torch.float64, device=self.state.device)
         a.x = _ptr(self.x)
-        self.keep = (A, At, Hc, Hd, lb, ub, P)
+        self.keep = (A, At, Hc, Hd, lb, ub, P, LR)
         return True
+
+    def _bind_lowrank(self, LR):
+        """ipx_cg_args.LR_*: the low-rank term's buffers (its memory: the same for a whole solve)"""
+        a = self.args
+        if LR is None:
+            a.LR_W = a.LR_state = a.LR_part = None
+            a.LR_mem = a.LR_rows = 0
+            return
+        m = LR.mem
+        a.LR_W, a.LR_state, a.LR_part = _ptr(m.W), _ptr(m.state), _ptr(m.part)
+        a.LR_mem, a.LR_rows = m.strategy.memory, m.n
+
+    def _part1_doubles(self, count):
+        """2 x the p'Hp partials the Hessian's product writes (a low-rank term: one per
+        workgroup of its second kernel)"""
+        lr = self.lowrank
+        if lr is not None:
+            count = max(count, _hip.load().ipx_lowrank_grid(lr.mem.n))
+        return 2 * max(count, 1)
 
     def __init__(self, H, P, lb, ub, resident=None):
         from .dense import DeviceDense
@@ -498,9 +550,10 @@ class _Loop:
         lib = _hip.load()
         A = P.A
         At = A.T
-        parts = _hessian_parts(H)
+        parts = _loop_parts(H)
         self.operator = None if parts is not None else H
-        Hc, Hd = parts if parts is not None else (None, None)
+        Hc, Hd, LR = parts if parts is not None else (None, None, None)
+        self.lowrank = LR
         self.n, self.m = P.n, P.m
         n, m = self.n, self.m
         dev = ctx().device
@@ -514,18 +567,22 @@ class _Loop:
         self.t = torch.empty(m, dtype=f64, device=dev)
         self.state = torch.zeros(lib.ipx_cg_state_size(), dtype=f64, device=dev)
         grid = lib.ipx_cg_vec_grid(n)
-        self.part1 = torch.zeros(2 * (Hc.pattern.ntiles if Hc is not None else 1), dtype=f64,
-                                 device=dev)
+        self.part1 = torch.zeros(self._part1_doubles(Hc.pattern.ntiles if Hc is not None else 1),
+                                 dtype=f64, device=dev)
         # (box-Schur projection: step1 writes one partial per >= 1280 elements, csrc/cg.hip SB_RMIN)
         self.part2 = torch.zeros(2 * max(grid, A.pattern.ntiles, n // 1024 + 2), dtype=f64,
                                  device=dev)
         self.part3 = torch.zeros(2 * max(At.pattern.ntiles, (m + 255) // 256 + 1, n // 1024 + 2),
                                  dtype=f64, device=dev)
         self.part4 = torch.zeros((m + 255) // 256 + 1, dtype=f64, device=dev)   # ||w-(AA')v||^2 partials
-        self.keep = (A, At, Hc, Hd, lb, ub, P)
+        self.keep = (A, At, Hc, Hd, lb, ub, P, LR)
         a = CgArgs()
+        self.args = a
         a.n, a.m = n, m
         for pre, M in (("A", A), ("At", At), ("H", Hc)):
+            if M is None and LR is not None:      # low-rank term (+ diagonal) alone
+                a.H_ntiles = 1
+                continue
             if M is None:                 # operator Hessian: applied by the host (H_operator)
                 a.H_ntiles, a.H_operator = 1, 1
                 continue
@@ -536,6 +593,7 @@ class _Loop:
             setattr(a, pre + "_tiles", _ptr(pat.tiles))
             setattr(a, pre + "_ntiles", pat.ntiles)
         a.H_diag = _ptr(Hd.t) if Hd is not None else None
+        self._bind_lowrank(LR)
         a.solver_kind = _solver_kind(P.solver)
         if a.solver_kind == 1:
             a.banded = ctypes.cast(ctypes.pointer(P.solver.c_args()), ctypes.c_void_p)
@@ -631,20 +689,28 @@ class _Loop:
         self.part1, self.part3, self.part4 = z(2 * 2048), z(2 * 2048), z(2 * 2048)
         self.part2 = z(2 * grid)
         a = CgArgs()
+        self.args = a
         a.n, a.m = n, m
         a.A_val, a.At_val = _ptr(A.t), _ptr(At.t)
         Hd_ = _dense_hessian(H)
+        self.lowrank = None
         if Hd_ is not None:
             a.H_val = _ptr(Hd_.t)
             self.keep = (A, At, Hd_, lb, ub, P)
         else:
-            Hc, Hd = _hessian_parts(H)
-            pat = Hc.pattern
-            a.H_rowptr, a.H_colidx, a.H_val = _ptr(pat.indptr), _ptr(pat.indices), _ptr(Hc.val)
-            a.H_tiles, a.H_ntiles = _ptr(pat.tiles), pat.ntiles
+            Hc, Hd, LR = _loop_parts(H)
+            self.lowrank = LR
+            if Hc is not None:
+                pat = Hc.pattern
+                a.H_rowptr, a.H_colidx, a.H_val = _ptr(pat.indptr), _ptr(pat.indices), _ptr(Hc.val)
+                a.H_tiles, a.H_ntiles = _ptr(pat.tiles), pat.ntiles
+                self.part1 = z(self._part1_doubles(pat.ntiles))
+            else:
+                a.H_ntiles = 1
+                self.part1 = z(max(self._part1_doubles(1), 2 * 2048))
             a.H_diag = _ptr(Hd.t) if Hd is not None else None
-            self.part1 = z(2 * max(pat.ntiles, 1))
-            self.keep = (A, At, Hc, Hd, lb, ub, P)
+            self._bind_lowrank(LR)
+            self.keep = (A, At, Hc, Hd, lb, ub, P, LR)
         a.banded = ctypes.c_void_p(P.solver.Ginv.t.data_ptr())
         a.solver_kind = 2
         for name in ("x", "p", "r", "Hp", "w", "v", "t", "state",
@@ -807,7 +873,7 @@ def _projected_cg(H, c, Z, Y, b, trust_radius, lb, ub, tol, max_iter, max_infeas
         st = stream_ptr()
         a = L.args
         if isinstance(P.A, DeviceCSR) and a.solver_kind in (0, 1) and getattr(P.solver, "perm", None) is None \
-                and a.banded and not getattr(P.solver, "refine_steps", 0) \
+                and a.banded and not getattr(P.solver, "refine_steps", 0) and L.lowrank is None \
                 and lib.ipx_cg_prime_ws_doubles(L.ref(), P.A.pattern.ntiles) <= 65536:   # (IPX_WS_DOUBLES)
             # the whole priming behind one C call, into the loop's own buffers
             ctx_ = ctx()

@@ -21,6 +21,7 @@ from .barrier import tr_interior_point
 from .canonical import lagrangian_hessian, to_canonical, empty_canonical_constraint
 from .constraints import (NonlinearConstraint, LinearConstraint, BoxConstraint, wrap_hessian)
 from .fd import FiniteDifferenceOperator, FD_METHODS
+from . import quasi_newton as _qn
 from .sqp import equality_constrained_sqp
 
 __all__ = ['minimize_constrained']
@@ -111,7 +112,12 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
     from . import device_mode as dm
     if xp.name != "hip":
         raise RuntimeError("device-callback mode needs the HIP backend")
-    if hess in FD_METHODS:           # N4: differences of the device gradient callback
+    qn_memory = None
+    if _qn.is_strategy(hess):
+        # the gradient at every accepted point is the one the solver evaluated there
+        grad = _qn.DeviceGradientMemo(grad)
+        hess, qn_memory = _qn.device_hessian(hess, grad, x0.numel())
+    elif hess in FD_METHODS:           # N4: differences of the device gradient callback
         from .fd import DeviceFiniteDifferenceOperator
         fd_method = hess
         hess = lambda xt: DeviceFiniteDifferenceOperator(grad, dm.as_dvec(xt), fd_method)
@@ -159,6 +165,8 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
     result.execution_time = time.time() - start_time
     result.method = method
     result.message = TERMINATION_MESSAGES[result.status]
+    if qn_memory is not None:
+        result.hess_updates, result.hess_skipped = qn_memory.counts()
     for k in _VECTOR_FIELDS:
         if k in result and hasattr(result[k], "t"):
             result[k] = result[k].t
@@ -384,11 +392,18 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     """
     options = dict(options)
     shard = _shard_request(options)
+    if _qn.is_strategy(hess) and options.get("constant_hessian", False):
+        raise ValueError("options={'constant_hessian': True} cannot be combined with a "
+                         "quasi-Newton hess (%r): its approximation changes at every step" % (hess,))
     # (an ADDITIVE option, see below; popped before any dispatch so that it never reaches the
     # outer loops' keyword arguments: device-callback mode keeps its Hessians on the device
     # anyway, and a non-callable ``hess`` -- finite differences, quasi-Newton -- has no constant
     # value to keep)
     constant_hessian = bool(options.pop("constant_hessian", False))
+    if _qn.is_strategy(hess) and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
+                                  "row-sharded backend; pass an exact Hessian or finite "
+                                  "differences ('2-point', '3-point', 'cs')" % (hess,))
     if hasattr(x0, "sh") and hasattr(x0, "owns"):
         # a DISTRIBUTED start vector (sharded.ShardVec): device-callback mode on the row-sharded
         # backend -- the callbacks take and return distributed objects, nothing is gathered
@@ -411,7 +426,9 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
 
     def plain_grad(x):
         return np.atleast_1d(grad(x))
-    grad_wrapped = _Memoize(plain_grad, x0, g0) if hess in FD_METHODS else plain_grad
+    grad_wrapped = (_Memoize(plain_grad, x0, g0) if hess in FD_METHODS or _qn.is_strategy(hess)
+                    else plain_grad)
+    qn_memory = None
 
     if callable(hess) and constant_hessian:
         # ADDITIVE option (the reference has none; its signature is unchanged): the objective's
@@ -431,6 +448,8 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     elif hess in FD_METHODS:
         def hess_wrapped(x):
             return FiniteDifferenceOperator(grad_wrapped, x, hess)
+    elif _qn.is_strategy(hess):
+        hess_wrapped, qn_memory = _qn.host_hessian(hess, grad_wrapped, n_vars)
     else:
         hess_wrapped = hess
 
@@ -551,6 +570,8 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     result.execution_time = time.time() - start_time         # :548-564
     result.method = method
     result.message = TERMINATION_MESSAGES[result.status]
+    if qn_memory is not None:
+        result.hess_updates, result.hess_skipped = qn_memory.counts()
     for k in _VECTOR_FIELDS:
         if k in result:
             result[k] = xp.tohost(result[k])

@@ -35,9 +35,12 @@ class DeviceHessian:
     reference does.
     """
 
-    def __init__(self, n, csr=None, diag=None, others=(), merge=True):
+    def __init__(self, n, csr=None, diag=None, others=(), merge=True, lowrank=None):
         self.n = n
         self.shape = (n, n)
+        # a low-rank term (quasi_newton.LowRankTerm) on the first lowrank.shape[0] rows: the
+        # device CG loop adds it behind the product of the other parts (ipx_cg_args.LR_*)
+        self.lowrank = lowrank
         if csr is not None and diag is not None and merge:
             # a CSR term that has every diagonal entry takes the diagonal terms into its values
             # (one scatter-add per Hessian, on a copy: the caller's matrix is not touched): the
@@ -62,6 +65,9 @@ class DeviceHessian:
             out = self.diag * p
         else:
             out = DVec.zeros(self.n)
+        if self.lowrank is not None:
+            rows = self.lowrank.shape[0]
+            self.lowrank.dot(p[:rows], out=out[:rows], accumulate=True)
         for h in self.others:
             out = out + h.dot(p)
         return out
