@@ -42,7 +42,10 @@ constexpr int BJ = 32;           // block size of the block-Jacobi preconditione
 
 // One workgroup of BJ x BJ lanes per block: S_b = A_b A_b' (rows order[b*BJ + s], s < BJ;
 // order < 0: an identity row), Cholesky, explicit inverse -> binv[b] (BJ x BJ, symmetric).
-// flag != 0 afterwards: a pivot was not positive (rows of the block linearly dependent).
+// flag afterwards: bit 1, a pivot was not positive (no factorization); bit 2, a positive pivot
+// lost 43 bits against its diagonal entry (IPX_PIVOT_RTOL, as ipx_chol_factor): rows of the
+// block linearly dependent up to rounding -- the elimination of an exact dependency seldom
+// leaves an exact zero.
 __global__ void __launch_bounds__(BJ *BJ)
 k_blockjacobi_build(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
                     const double *__restrict__ val, const int32_t *__restrict__ order,
@@ -73,6 +76,7 @@ k_blockjacobi_build(const int32_t *__restrict__ rowptr, const int32_t *__restric
     if (r == j && c == j) {
       const double d = T[j][j];
       if (!(d > 0.0)) atomicOr(flag, 1);
+      else if (!(d > IPX_PIVOT_RTOL * s)) atomicOr(flag, 2);     // (s: this lane's T[j][j])
       T[j][j] = sqrt(d > 0.0 ? d : 1.0);
     }
     __syncthreads();

@@ -35,6 +35,19 @@ def wrap_hessian(hess, sample, nargs):
     return lambda *a: np.atleast_2d(np.asarray(hess(*a)))
 
 
+def canonical_csr(M):
+    """``M`` as a CSR matrix in canonical format: column indices sorted within every row and
+    no (row, column) entry stored twice.  scipy defines repeated entries as summed; the device
+    assembly of ``A A'`` (merge joins of sorted rows) and every symbolic analysis of a pattern
+    assume each entry once, so repeats are summed here, on a copy: the caller's matrix is never
+    changed.  A matrix that is canonical already is returned as is (no copy of its arrays)."""
+    M = sps.csr_matrix(M)
+    if not M.has_canonical_format:
+        M = M.copy()
+        M.sum_duplicates()
+    return M
+
+
 def check_kind(kind, m):
     """Validate / broadcast ``kind`` (reference _constraints.py:370-411)."""
     if not isinstance(kind, (tuple, list, str)):
@@ -144,8 +157,8 @@ class NonlinearConstraint(_Initialised):
         self.sparse_jacobian = bool(sparse_jacobian
                                     or (sparse_jacobian is None and sps.issparse(J0)))
         if self.sparse_jacobian:
-            self.jac = lambda x: sps.csr_matrix(self._jac(x))
-            self.J0 = sps.csr_matrix(J0)
+            self.jac = lambda x: canonical_csr(self._jac(x))
+            self.J0 = canonical_csr(J0)
         else:
             def dense_jac(x):
                 J = self._jac(x)
@@ -182,7 +195,7 @@ class LinearConstraint(_Initialised):
         self.sparse_jacobian = bool(sparse_jacobian
                                     or (sparse_jacobian is None and sps.issparse(self.A)))
         if self.sparse_jacobian:
-            self.A = sps.csr_matrix(self.A)
+            self.A = canonical_csr(self.A)
         else:
             self.A = self.A.toarray() if sps.issparse(self.A) else np.atleast_2d(self.A)
         x0 = np.atleast_1d(x0).astype(float)

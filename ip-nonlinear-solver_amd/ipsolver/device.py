@@ -567,6 +567,30 @@ class CSRPattern:
             self._diag_pos = pos
         return self._diag_pos
 
+    def sort_info(self):
+        """(None, None) when the column indices of every row increase strictly, else (the
+        sorted pattern, the device permutation of the values that sorts them); computed once
+        per pattern.  Raises ValueError naming the first (row, column) entry stored twice."""
+        info = getattr(self, "_ipx_sorted", None)
+        if info is None:
+            rows = np.repeat(np.arange(self.shape[0], dtype=np.int64), np.diff(self.indptr_h))
+            key = rows * max(self.shape[1], 1) + self.indices_h.astype(np.int64)
+            if np.all(np.diff(key) > 0):
+                info = (None, None)
+            else:
+                order = np.argsort(key, kind="stable")
+                rep = np.flatnonzero(np.diff(key[order]) == 0)
+                if len(rep):
+                    e = order[rep[0]]
+                    raise ValueError(
+                        "CSRPattern: entry (%d, %d) is stored more than once; a device pattern "
+                        "must hold every (row, column) entry once (sum repeated entries first)"
+                        % (rows[e], self.indices_h[e]))
+                spat = CSRPattern(self.indptr_h, self.indices_h[order], self.shape)
+                info = (spat, torch.from_numpy(order).to(ctx().device))
+            self._ipx_sorted = info
+        return info
+
     def same_as(self, indptr, indices):
         return (len(indptr) == len(self.indptr_h) and len(indices) == len(self.indices_h)
                 and np.array_equal(indptr, self.indptr_h)
@@ -617,10 +641,8 @@ class DeviceCSR:
 
     @staticmethod
     def from_scipy(M, pattern=None, row_breaks=None):
-        import scipy.sparse as sps
-        M = sps.csr_matrix(M)
-        if not M.has_sorted_indices:
-            M = M.sorted_indices()
+        from .constraints import canonical_csr
+        M = canonical_csr(M)            # (sorted, repeated entries summed)
         if pattern is None or not pattern.same_as(M.indptr, M.indices):
             pattern = CSRPattern(M.indptr, M.indices, M.shape, row_breaks=row_breaks)
         val = torch.from_numpy(np.ascontiguousarray(M.data, dtype=np.float64)).to(ctx().device)
@@ -635,19 +657,10 @@ class DeviceCSR:
         """This matrix with the column indices of every row in increasing order (the
         normal-equation assembly merges sorted rows).  Matrices built by ``from_scipy`` are
         sorted already; a hand-made pattern is checked once and, if need be, re-ordered
-        through a cached permutation of the values."""
-        pat = self.pattern
-        info = getattr(pat, "_ipx_sorted", None)
-        if info is None:
-            rows = np.repeat(np.arange(pat.shape[0], dtype=np.int64), np.diff(pat.indptr_h))
-            key = rows * max(pat.shape[1], 1) + pat.indices_h.astype(np.int64)
-            if np.all(np.diff(key) >= 0):
-                info = (None, None)
-            else:
-                order = np.argsort(key, kind="stable")
-                spat = CSRPattern(pat.indptr_h, pat.indices_h[order], pat.shape)
-                info = (spat, torch.from_numpy(order).to(ctx().device))
-            pat._ipx_sorted = info
+        through a cached permutation of the values.  A pattern that stores some (row, column)
+        entry twice is refused (ValueError): ``from_scipy`` sums such repeats, a device pattern
+        would have to be summed on every evaluation."""
+        info = self.pattern.sort_info()
         if info[0] is None:
             return self
         return DeviceCSR(info[0], self.val[info[1]])

@@ -11,6 +11,9 @@ iterations:
     NonlinearConstraint.fun(x) -> 1-D tensor
     NonlinearConstraint.jac(x) -> DeviceCSR (a fixed CSRPattern, values refreshed) |
                                   2-D CUDA tensor / DeviceDense (dense), any ``kind``
+                                  (a CSRPattern must store each (row, column) entry once:
+                                  a repeated entry is a ValueError; scipy matrices have
+                                  their repeats summed)
     NonlinearConstraint.hess(x, v) -> DeviceCSR | 1-D tensor (diagonal) | None
     LinearConstraint(A)  with A a scipy sparse matrix, a DeviceCSR, or a 2-D CUDA tensor /
                          DeviceDense (dense), any ``kind``
@@ -255,7 +258,7 @@ class _DeviceConstraint:
         elif isinstance(user, LinearConstraint):
             from .dense import DeviceDense
             if isinstance(user.A, (DeviceCSR, DeviceDense)):
-                A = user.A
+                A = _check_jac(user.A)
             elif torch.is_tensor(user.A) and user.A.dim() == 2:
                 if not user.A.is_cuda:
                     raise TypeError("device-callback mode: a dense LinearConstraint matrix must "
@@ -332,6 +335,8 @@ def _check_jac(J):
     if not isinstance(J, (DeviceCSR, DeviceDense)):
         raise TypeError("device-callback mode: `jac` must return an ipsolver.device.DeviceCSR "
                         "(or, for a dense Jacobian, a 2-D CUDA tensor / DeviceDense)")
+    if isinstance(J, DeviceCSR):
+        J.pattern.sort_info()           # (once per pattern: a repeated entry is a ValueError)
     return J
 
 

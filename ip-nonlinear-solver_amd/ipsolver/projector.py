@@ -558,9 +558,13 @@ class IterativeNormalSolver:
             pat = A.pattern
             _hip.call("ipx_blockjacobi_build", nblk, _p(pat.indptr), _p(pat.indices), _p(A.val),
                       _p(self.border), _p(self.binv), _p(flag), stream_ptr())
-            if int(flag.item()) != 0:
+            fl = int(flag.item())
+            if fl & 1:
                 raise np.linalg.LinAlgError("Singular Jacobian matrix: a diagonal block of A A' "
                                             "is not positive definite")
+            # bit 2 alone: every pivot positive, one lost 43 bits (a block numerically rank
+            # deficient); the solve goes on, as with the dense factorization
+            self.ill_conditioned = bool(fl & 2)
             self.z, self.part3 = z(m), z(nblk // 8 + 2)
             self.dinv = DVec.zeros(m)             # (r'z comes from the block kernel)
             a.dinv = self.dinv.t.data_ptr()
