@@ -245,6 +245,9 @@ int ipx_banded_pcr_level(void *handle);
  * contraction bound.  ipx_banded_status returns IPX_EUNSUPPORTED for half bandwidth 5..8
  * when the bound is >= 0.5: the caller takes another solver. */
 int ipx_banded_refine_steps(void *handle, double *eta);
+/* Rows per chunk of level 0 (interior rows + half bandwidth): the last chunk takes the
+ * m mod q (or q) rows that are left. */
+int ipx_banded_chunk_rows(void *handle);
 int ipx_banded_solve(void *handle, const double *w, double *x, void *stream);
 /* Same, skipped on the device when *guard != 0 (stop flag of the CG loops). */
 int ipx_banded_solve_guarded_c(void *handle, const double *w, double *x, const double *guard,

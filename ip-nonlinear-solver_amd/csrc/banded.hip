@@ -1437,7 +1437,8 @@ __device__ __forceinline__ double pcr_rcp(double b) {
 
 // Factor-time check in ONE launch: the reduction of the matrix alone (no right-hand side) on
 // the same windows as the solve, all PCR_LMAX levels; a workgroup tests its own rows after
-// every level: flags[s + 1] = a coupling at distance 2^s is still above 2^-56 of the diagonal,
+// every level: flags[s + 1] = a coupling at distance 2^s is still above 2^-56 of the diagonal
+// entry of either row it couples,
 // flags[PCR_LMAX + 1 + s + 1] = a reduced diagonal entry is not positive.  Plain stores of the
 // constant 1, one word per (level, finding): every workgroup raises the first kind below the
 // decoupling level, and atomics on ONE word serialise in L2 at ~45 ns each -- 71 us of this
@@ -1490,7 +1491,13 @@ k_pcr_check(int m, int rows_wg, const double *__restrict__ band, int *flags) {
       bn = __builtin_fma(ga, ahi, bn);
       a[k] = al * alo; b[k] = bn;
       if (own[k]) {
-        if (!(fabs(a[k]) <= tiny * bn)) bits |= 1;
+        // a coupling is tested against the diagonal entries of BOTH its rows: a[k] (to row
+        // i - 2h) here, and the coupling to row i + 2h -- formed as row i + 2h forms its own
+        // a[k], bit for bit -- against this row's bn as well.  Tested on one side only, rows
+        // scaled up along the band passed with couplings far above 2^-56 of the smaller
+        // diagonal entry (an inexact solve at a level too low).  (r + 2h < PAD + R + PAD.)
+        const double aup = (-pa[cur][r + 2 * h] * rhi) * ahi;
+        if (!(fmax(fabs(a[k]), fabs(aup)) <= tiny * bn)) bits |= 1;
         if (!(bn > 0.0)) bits |= 2;
         // a reduced diagonal entry -- 1 / (S^-1)_ii in the limit, never above the pivot an
         // elimination in any order leaves for row i -- lost 43 bits against the entry itself:
@@ -2520,6 +2527,10 @@ int ipx_banded_refine_steps(void *handle, double *eta) {
 // Level at which the cyclic reduction of this factorization's matrix has decoupled (the
 // single-launch solve then runs as parallel cyclic reduction); 0 when that path is off.
 int ipx_banded_pcr_level(void *handle) { return handle ? ((Banded *)handle)->pcr_L : 0; }
+
+// Rows per chunk of level 0, q = c + k (the single-launch solve takes DEC_CHUNKS of them per
+// workgroup); 0 without a handle.
+int ipx_banded_chunk_rows(void *handle) { return handle ? ((Banded *)handle)->lev[0].q : 0; }
 
 // x = S^-1 w.  w and x are length m; x may alias w.
 int ipx_banded_solve(void *handle, const double *w, double *x, void *stream) {

@@ -179,3 +179,105 @@ def worst(got, val, mag, k):
     excess = np.abs(np.asarray(got) - val) - gamma(k) * mag
     idx = np.unravel_index(np.argmax(excess), np.shape(excess))
     return idx, np.asarray(got)[idx], val[idx], float(np.max(excess))
+
+
+# ------------------------------------------------- solves with S = A A': exact residuals
+# A = diag(2^e) A_int with A_int integer: every product a_it a_jt is an integer times
+# 2^(e_i + e_j), so S = A A' is exactly representable, the device assembles it exactly (any
+# summation order), and the residual r = w - S v of a computed solve is evaluated exactly.
+def pow2_rows(A_int, e):
+    """diag(2^e) A_int, exactly (CSR)."""
+    A = sps.csr_matrix(A_int, copy=True)
+    A.data = np.ldexp(A.data, np.repeat(np.asarray(e, dtype=np.int64), np.diff(A.indptr)))
+    return A
+
+
+def gram_pow2(A_int, e=None):
+    """S = A A' of A = diag(2^e) A_int as a CSR float64 matrix, exactly: the int64 product of
+    the integer rows, each entry times 2^(e_i + e_j) (both steps checked)."""
+    A = sps.csr_matrix(A_int)
+    Ai = sps.csr_matrix((A.data.astype(np.int64), A.indices, A.indptr), shape=A.shape)
+    assert np.array_equal(Ai.data, A.data), "A_int is not integer-valued"
+    S = (Ai @ Ai.T).tocoo()
+    assert S.nnz == 0 or np.abs(S.data).max() < 2 ** 53
+    e = np.zeros(A.shape[0], np.int64) if e is None else np.asarray(e, dtype=np.int64)
+    ex = e[S.row] + e[S.col]
+    val = np.ldexp(S.data.astype(np.float64), ex)
+    assert np.array_equal(np.ldexp(val, -ex), S.data.astype(np.float64)), \
+        "S is not exactly representable"
+    out = sps.csr_matrix((val, (S.row, S.col)), shape=S.shape)
+    out.sort_indices()
+    return out
+
+
+def split26(v):
+    """Veltkamp's split v = hi + lo (exactly), both halves of at most 26 significant bits."""
+    v = np.asarray(v, dtype=np.float64)
+    c = v * 134217729.0                                      # 2^27 + 1
+    hi = c - (c - v)
+    return hi, v - hi
+
+
+def assert_26_bits(x):
+    """Every entry is an integer below 2^26 times a power of two (or 0)."""
+    mant, _ = np.frexp(np.asarray(x, dtype=np.float64))
+    scaled = np.ldexp(mant, 26)
+    assert np.array_equal(scaled, np.round(scaled)), "an entry has more than 26 significant bits"
+
+
+def residual_exact(S, v, w):
+    """r = w - S v with every entry correctly rounded.  S_ij has at most 26 significant bits
+    (asserted) and v_j is split into two halves of 26 bits, so every S_ij v_half is exact and
+    ``math.fsum`` of w_i and the products of row i is the correctly rounded r_i."""
+    S = sps.csr_matrix(S)
+    assert_26_bits(S.data)
+    v = np.asarray(v, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    hi, lo = split26(v)
+    assert np.array_equal(hi + lo, v)
+    ph = (-S.data * hi[S.indices]).tolist()
+    pl = (-S.data * lo[S.indices]).tolist()
+    ip = S.indptr.tolist()
+    wl = w.tolist()
+    return np.array([math.fsum([wl[i]] + ph[ip[i]:ip[i + 1]] + pl[ip[i]:ip[i + 1]])
+                     for i in range(S.shape[0])])
+
+
+def pow2_scale(S):
+    """f with Delta = diag(2^f), f_i = floor(log2 sqrt(S_ii) + 1/2): powers of two, so the
+    scaled system (Delta^-1 S Delta^-1)(Delta v) = Delta^-1 w is formed without rounding, and
+    rows scaled by 2^e shift f by e exactly."""
+    d = np.asarray(sps.csr_matrix(S).diagonal(), dtype=np.float64)
+    assert np.all(d > 0)
+    return np.floor(0.5 * np.log2(d) + 0.5).astype(np.int64)
+
+
+def scaled_matrix(S):
+    """Delta^-1 S Delta^-1 (CSR), exact."""
+    S = sps.csr_matrix(S)
+    f = pow2_scale(S)
+    rows = np.repeat(np.arange(S.shape[0]), np.diff(S.indptr))
+    return sps.csr_matrix((np.ldexp(S.data, -(f[rows] + f[S.indices])), S.indices, S.indptr),
+                          shape=S.shape)
+
+
+def backward_error(S, v, w, r=None):
+    """Normwise backward error of v for the diagonally scaled system (Delta: pow2_scale),
+        eta = ||D^-1 r||_inf / (||D^-1 S D^-1||_inf ||D v||_inf + ||D^-1 w||_inf),
+    r the exact residual (residual_exact, or given).  Rows of A scaled by powers of two change
+    it only through rounding."""
+    S = sps.csr_matrix(S)
+    if r is None:
+        r = residual_exact(S, v, w)
+    f = pow2_scale(S)
+    normS = float(np.max(np.asarray(abs(scaled_matrix(S)).sum(axis=1)).ravel()))
+    num = float(np.max(np.abs(np.ldexp(r, -f))))
+    den = normS * float(np.max(np.abs(np.ldexp(v, f)))) + \
+        float(np.max(np.abs(np.ldexp(w, -f))))
+    return num / den if den > 0 else 0.0
+
+
+def scaled_cond(S):
+    """kappa_2(Delta^-1 S Delta^-1), host float64 (dense: for the sizes the dense solver takes)."""
+    ev = np.linalg.eigvalsh(scaled_matrix(S).toarray())
+    return float(ev[-1] / ev[0])
