@@ -777,6 +777,46 @@ int ipx_lowrank_apply(int64_t n, int32_t mem, const double *W, const double *sta
 void ipx_lowrank_middle_host(int32_t kind, int32_t mem, double init_scale, double threshold,
                              double *state, const double *dots);
 
+/* ---- sparse finite-difference Jacobians (csrc/fdjac.hip, ipsolver/fd_jacobian.py) ----
+ * Curtis-Powell-Reid grouped differences of a constraint function on a fixed CSR pattern
+ * (reference _numdiff.py:15-103, 484-561).  method: 0 '2-point', 1 '3-point', 2 'cs'; one_sided
+ * are bytes (0 / 1); groups[n] holds the group of every column.  Every value is computed with the
+ * reference's operations in the reference's order (elementwise, one rounding each): the results
+ * are its bits.  The *_host entries run the same inline functions on host arrays.
+ *
+ * steps: h = (rel * sign(x0)) * max(1, |x0|) with sign(0) = +1 (rel_vec, when not NULL, gives rel
+ * per variable), then _adjust_scheme_to_bounds with num_steps = 1: '1-sided' for method 0,
+ * '2-sided' for method 1, nothing for method 2.  lb / ub NULL: no bound on that side. */
+int ipx_fd_steps(int64_t n, int32_t method, double rel, const double *rel_vec, const double *x0,
+                 const double *lb, const double *ub, double *h, unsigned char *one_sided,
+                 void *stream);
+void ipx_fd_steps_host(int64_t n, int32_t method, double rel, const double *rel_vec,
+                       const double *x0, const double *lb, const double *ub, double *h,
+                       unsigned char *one_sided);
+/* the perturbed point(s) of group g, whole vectors: method 0: x1 = x0 + h [groups == g];
+ * method 1: x1 / x2 by the one-sided and central rules; method 2: x1 = h [groups == g] (the
+ * imaginary part of the complex point; x2 unused).  dx[j] is written for the members of g only
+ * (x1 - x0, x2 - x0 or x2 - x1, from the perturbed point; h for method 2). */
+int ipx_fd_perturb(int64_t n, int32_t method, int32_t g, const int32_t *groups, const double *x0,
+                   const double *h, const unsigned char *one_sided, double *x1, double *x2,
+                   double *dx, void *stream);
+void ipx_fd_perturb_host(int64_t n, int32_t method, int32_t g, const int32_t *groups,
+                         const double *x0, const double *h, const unsigned char *one_sided,
+                         double *x1, double *x2, double *dx);
+/* val[k] = df / dx[col[k]] for every stored entry k whose column's group lies in [g_lo, g_hi),
+ * one launch over the pattern's SpMV row tiles (ipx_csr_tiles_host); other entries are left as
+ * they are.  F1 / F2: (g_hi - g_lo) planes of m function values, plane g - g_lo = the values at
+ * group g's perturbed point(s) (F2 for method 1 only; F1 the imaginary parts for method 2). */
+int ipx_fd_assemble(int64_t m, int64_t n, const int32_t *rowptr, const int32_t *colidx,
+                    const int32_t *tiles, int32_t ntiles, int32_t method, const int32_t *groups,
+                    int32_t g_lo, int32_t g_hi, const double *f0, const double *F1,
+                    const double *F2, const double *dx, const unsigned char *one_sided,
+                    double *val, void *stream);
+void ipx_fd_assemble_host(int64_t m, int64_t n, const int32_t *rowptr, const int32_t *colidx,
+                          int32_t method, const int32_t *groups, int32_t g_lo, int32_t g_hi,
+                          const double *f0, const double *F1, const double *F2, const double *dx,
+                          const unsigned char *one_sided, double *val);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,10 @@ _SIGNATURES = {
     "ipx_lowrank_grid": [_I64],
     "ipx_lowrank_update": [_I32, _I64, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P],
     "ipx_lowrank_apply": [_I64, _I32, _P, _P, _P, _P, _I32, _P, _P],
+    "ipx_fd_steps": [_I64, _I32, _F64, _P, _P, _P, _P, _P, _P, _P],
+    "ipx_fd_perturb": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ipx_fd_assemble": [_I64, _I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P,
+                        _P, _P],
 }
 _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_launch_count": _c.c_longlong, "ipx_read_count": _c.c_longlong,
@@ -139,7 +143,8 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_sqp_part_doubles": _I64, "ipx_sqp_model_host": None, "ipx_sqp_ratio_host": None,
              "ipx_sqp_radius_host": None, "ipx_sqp_box_sphere_host": None,
              "ipx_lowrank_state_doubles": _I64, "ipx_lowrank_part_doubles": _I64,
-             "ipx_lowrank_middle_host": None}
+             "ipx_lowrank_middle_host": None, "ipx_fd_steps_host": None,
+             "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None}
 _EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
                    "ipx_dense_padded": [_I64], "ipx_gram_ws_doubles": [_I64, _I32],
                    "ipx_peer_create": [_I32, _I32, _I64],
@@ -150,7 +155,11 @@ _EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy"
                    "ipx_sqp_model_host": [_P], "ipx_sqp_ratio_host": [_P],
                    "ipx_sqp_radius_host": [_P], "ipx_sqp_box_sphere_host": [_P, _F64, _c.c_int, _P],
                    "ipx_lowrank_state_doubles": [_I32], "ipx_lowrank_part_doubles": [_I64, _I32],
-                   "ipx_lowrank_middle_host": [_I32, _I32, _F64, _F64, _P, _P]}
+                   "ipx_lowrank_middle_host": [_I32, _I32, _F64, _F64, _P, _P],
+                   "ipx_fd_steps_host": [_I64, _I32, _F64, _P, _P, _P, _P, _P, _P],
+                   "ipx_fd_perturb_host": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+                   "ipx_fd_assemble_host": [_I64, _I64, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P,
+                                            _P, _P, _P]}
 
 _lib = None
 

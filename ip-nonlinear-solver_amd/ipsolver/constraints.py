@@ -137,31 +137,86 @@ class _Initialised:
         self.enforce_feasibility = check_enforce_feasibility(self.enforce_feasibility, self.m)
 
 
+def check_fd_jacobian_arguments(jac, hess, sparsity, rel_step):
+    """Construction-time checks of ``NonlinearConstraint``'s finite-difference arguments."""
+    if isinstance(jac, str):
+        if jac not in FD_METHODS:
+            raise ValueError("`jac` must be callable or one of %r, got %r" % (FD_METHODS, jac))
+        if jac == 'cs' and isinstance(hess, str) and hess in FD_METHODS:
+            raise ValueError("jac='cs' cannot be combined with a finite-difference `hess` (%r): "
+                             "complex steps do not nest; pass a callable `hess`, None, or use "
+                             "jac='2-point' / '3-point'" % (hess,))
+    elif sparsity is not None or rel_step is not None:
+        raise ValueError("`finite_diff_jac_sparsity` and `finite_diff_rel_step` apply to a "
+                         "finite-difference `jac` ('2-point', '3-point', 'cs') only; `jac` is "
+                         "callable")
+
+
+class _FDJacobian:
+    """``jac(x)`` by finite differences of ``fun`` (numpy callbacks): ``approx_derivative`` on a
+    plan built once.  ``nfev`` counts the calls of ``fun`` spent on differences: G per
+    evaluation (2 G for '3-point') plus one for ``f0`` at every point but ``x0`` ('2-point' and
+    '3-point'; 'cs' needs none)."""
+
+    def __init__(self, fun, method, sparsity, rel_step, n, m):
+        from ._numdiff import _plan_for
+        self.fun, self.method, self.rel_step = fun, method, rel_step
+        self.plan, self.dense = _plan_for(sparsity, n, m)
+
+    @property
+    def nfev(self):
+        return self.plan.nfev
+
+    def __call__(self, x, f0=None):
+        from ._numdiff import approx_derivative
+        if self.method == 'cs' and f0 is None:
+            f0 = np.zeros(self.plan.m)          # (not used by the complex step: spare the call)
+        return approx_derivative(self.fun, x, self.method, self.rel_step, f0,
+                                 sparsity=self.plan)
+
+
 class NonlinearConstraint(_Initialised):
     """``lb <= fun(x) <= ub`` style constraint (reference _constraints.py:14-167).
 
-    ``NonlinearConstraint(fun, kind, jac, hess='2-point', enforce_feasibility=False)``
+    ``NonlinearConstraint(fun, kind, jac, hess='2-point', enforce_feasibility=False,
+    finite_diff_jac_sparsity=None, finite_diff_rel_step=None)``
+
+    ``jac`` is a callable or '2-point' / '3-point' / 'cs': the Jacobian by finite differences of
+    ``fun`` (``_numdiff.approx_derivative``; scipy's keyword names).  ``finite_diff_jac_sparsity``
+    is a sparsity structure or ``(structure, groups)``; without it the difference is dense (n
+    evaluations; refused in device-callback mode).
     """
 
-    def __init__(self, fun, kind, jac, hess='2-point', enforce_feasibility=False):
+    def __init__(self, fun, kind, jac, hess='2-point', enforce_feasibility=False,
+                 finite_diff_jac_sparsity=None, finite_diff_rel_step=None):
+        check_fd_jacobian_arguments(jac, hess, finite_diff_jac_sparsity, finite_diff_rel_step)
         self._fun, self._jac, self._hess = fun, jac, hess
         self.kind = kind
         self.enforce_feasibility = enforce_feasibility
+        self.finite_diff_jac_sparsity = finite_diff_jac_sparsity
+        self.finite_diff_rel_step = finite_diff_rel_step
 
     def evaluate_and_initialize(self, x0, sparse_jacobian=None):
         x0 = np.atleast_1d(x0).astype(float)
         f0 = np.atleast_1d(self._fun(x0))
-        J0 = self._jac(x0)
+        if isinstance(self._jac, str):
+            user_jac = self.fd_jacobian = _FDJacobian(
+                lambda x: np.atleast_1d(self._fun(x)), self._jac, self.finite_diff_jac_sparsity,
+                self.finite_diff_rel_step, x0.size, f0.size)
+            J0 = user_jac(x0, f0)
+        else:
+            user_jac = self._jac
+            J0 = user_jac(x0)
 
         self.fun = lambda x: np.atleast_1d(self._fun(x))
         self.sparse_jacobian = bool(sparse_jacobian
                                     or (sparse_jacobian is None and sps.issparse(J0)))
         if self.sparse_jacobian:
-            self.jac = lambda x: canonical_csr(self._jac(x))
+            self.jac = lambda x: canonical_csr(user_jac(x))
             self.J0 = canonical_csr(J0)
         else:
             def dense_jac(x):
-                J = self._jac(x)
+                J = user_jac(x)
                 return J.toarray() if sps.issparse(J) else np.atleast_2d(J)
             self.jac = dense_jac
             self.J0 = J0.toarray() if sps.issparse(J0) else np.atleast_2d(J0)

@@ -273,6 +273,12 @@ class _DeviceConstraint:
         elif isinstance(user, NonlinearConstraint):
             ufun, ujac, uhess = user._fun, user._jac, user._hess
             self.fun = lambda x: as_dvec(ufun(x.t))
+            f0 = self.fun(x0)
+            if isinstance(ujac, str):
+                # the Jacobian by grouped differences of ``fun`` on the device (fd_jacobian.py):
+                # the plan -- ONE CSRPattern for the run -- is built here, the first evaluation
+                # uses the value the constraint already has at x0
+                ujac = self.fd_jacobian = _DeviceFDJacobian(user, ufun, n, len(f0), x0, f0)
             self.jac = lambda x: _check_jac(ujac(x.t))
             if uhess in ('2-point', '3-point', 'cs'):
                 # d/dx [J(x)' v] by differences (reference _constraints.py:136-146), on the device
@@ -281,7 +287,6 @@ class _DeviceConstraint:
                     lambda xt: _check_jac(ujac(xt)).T.dot(v), x, uhess)
             else:
                 self.hess = None if uhess is None else (lambda x, v: uhess(x.t, v.t))
-            f0 = self.fun(x0)
         else:
             raise ValueError("Unknown Constraint type.")
         m = len(f0)
@@ -324,6 +329,42 @@ class _DeviceConstraint:
     @property
     def n_ineq(self):
         return self.rows.n_ineq
+
+
+class _DeviceFDJacobian:
+    """``jac(x)`` of a NonlinearConstraint with ``jac='2-point'|'3-point'|'cs'`` in device-callback
+    mode: ``SparseFDPlan.evaluate`` on a plan built once.  ``nfev`` counts the calls of ``fun``
+    spent on differences: G per evaluation (2 G for '3-point') plus one for ``f0`` at every point
+    but ``x0`` ('cs' needs none)."""
+
+    def __init__(self, user, fun, n, m, x0, f0):
+        from ._numdiff import group_columns
+        from .fd_jacobian import SparseFDPlan
+        sparsity = user.finite_diff_jac_sparsity
+        if sparsity is None:
+            raise ValueError(
+                "device-callback mode: jac=%r needs `finite_diff_jac_sparsity` (a structure, or "
+                "(structure, groups)): a dense difference of a device constraint costs n = %d "
+                "calls of `fun` per Jacobian and an m x n buffer, and is refused" % (user._jac, n))
+        if not sps.issparse(sparsity) and len(sparsity) == 2:
+            structure, groups = sparsity
+        else:
+            structure, groups = sparsity, group_columns(sparsity)
+        self.plan = SparseFDPlan(structure, groups, n, m)
+        self.fun, self.method, self.rel_step = fun, user._jac, user.finite_diff_rel_step
+        self._at = (x0.t, f0.t)
+
+    @property
+    def nfev(self):
+        return self.plan.nfev
+
+    def __call__(self, xt):
+        f0 = None
+        if self._at is not None:
+            if xt is self._at[0]:
+                f0 = self._at[1]
+            self._at = None
+        return self.plan.evaluate(self.fun, xt, self.method, f0=f0, rel_step=self.rel_step)
 
 
 def _check_jac(J):

@@ -167,6 +167,7 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
     result.message = TERMINATION_MESSAGES[result.status]
     if qn_memory is not None:
         result.hess_updates, result.hess_skipped = qn_memory.counts()
+    _report_fd_jacobian_calls(result, canon.parts)
     for k in _VECTOR_FIELDS:
         if k in result and hasattr(result[k], "t"):
             result[k] = result[k].t
@@ -276,6 +277,21 @@ def _minimize_distributed(fun, x0, grad, hess, constraints, method, xtol, gtol, 
         sh, fun, grad, lagr_hess, con._fun, con._jac, x0, sh.full("col", float(bk[1])),
         sh.full("col", float(bk[2])), xtol=xtol, gtol=gtol, max_iter=max_iter, callback=callback,
         **options)
+
+
+def _constraint_list(constraints):
+    if isinstance(constraints, (NonlinearConstraint, LinearConstraint, BoxConstraint)):
+        return [constraints]
+    return list(constraints)
+
+
+def _report_fd_jacobian_calls(result, holders):
+    """``jac_fd_nfev``: the calls of constraint functions spent on finite-difference Jacobians
+    (not part of ``ncev`` / ``njev``, which keep the reference's meaning); present only when some
+    constraint had a string ``jac``."""
+    fd = [h.fd_jacobian for h in holders if getattr(h, "fd_jacobian", None) is not None]
+    if fd:
+        result.jac_fd_nfev = int(sum(f.nfev for f in fd))
 
 
 class _ConstantArray(np.ndarray):
@@ -404,6 +420,12 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "
                                   "differences ('2-point', '3-point', 'cs')" % (hess,))
+    fd_jac = [c._jac for c in _constraint_list(constraints)
+              if isinstance(c, NonlinearConstraint) and isinstance(c._jac, str)]
+    if fd_jac and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("jac=%r: finite-difference constraint Jacobians are not "
+                                  "available on the row-sharded backend; pass a callable `jac`"
+                                  % (fd_jac[0],))
     if hasattr(x0, "sh") and hasattr(x0, "owns"):
         # a DISTRIBUTED start vector (sharded.ShardVec): device-callback mode on the row-sharded
         # backend -- the callbacks take and return distributed objects, nothing is gathered
@@ -572,6 +594,7 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     result.message = TERMINATION_MESSAGES[result.status]
     if qn_memory is not None:
         result.hess_updates, result.hess_skipped = qn_memory.counts()
+    _report_fd_jacobian_calls(result, copied)
     for k in _VECTOR_FIELDS:
         if k in result:
             result[k] = xp.tohost(result[k])
