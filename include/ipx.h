@@ -816,6 +816,25 @@ void ipx_fd_assemble_host(int64_t m, int64_t n, const int32_t *rowptr, const int
                           int32_t method, const int32_t *groups, int32_t g_lo, int32_t g_hi,
                           const double *f0, const double *F1, const double *F2, const double *dx,
                           const unsigned char *one_sided, double *val);
+/* the symmetric assemble of a finite-difference Hessian (m = n; the pattern structurally
+ * symmetric; f0 / F1 / F2 values of the differenced gradient): with q_ij the quotient
+ * ipx_fd_assemble writes at (i, j), every stored entry k = (i, j) gets
+ *     val[slot ? slot[k] : k] (+)= 0.5 * q_ij [group(j) in range] + 0.5 * q_ji [group(i) in range]
+ * An entry both of whose groups are >= g_lo is written (added to when `accumulate`), any other
+ * is added to: chunks [g_lo, g_hi) launched in ascending order give the single launch's bits, and
+ * `slot` + `accumulate` add several terms into one value array on the union of their patterns
+ * (each launch touches a slot once).  Entries with neither group in range are left alone. */
+int ipx_fd_assemble_sym(int64_t n, const int32_t *rowptr, const int32_t *colidx,
+                        const int32_t *tiles, int32_t ntiles, int32_t method,
+                        const int32_t *groups, int32_t g_lo, int32_t g_hi, const double *f0,
+                        const double *F1, const double *F2, const double *dx,
+                        const unsigned char *one_sided, const int32_t *slot, int32_t accumulate,
+                        double *val, void *stream);
+void ipx_fd_assemble_sym_host(int64_t n, const int32_t *rowptr, const int32_t *colidx,
+                              int32_t method, const int32_t *groups, int32_t g_lo, int32_t g_hi,
+                              const double *f0, const double *F1, const double *F2,
+                              const double *dx, const unsigned char *one_sided,
+                              const int32_t *slot, int32_t accumulate, double *val);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,8 @@
 //   ipx_fd_perturb    the perturbed point(s) of ONE group + dx of its members (elementwise)
 //   ipx_fd_assemble   val[k] = df / dx[col[k]] for every stored entry, in CSR order over the
 //                     pattern's SpMV row tiles: one launch per Jacobian (or per chunk of groups)
+//   ipx_fd_assemble_sym  the same for a Hessian (the Jacobian of a gradient) on a symmetric
+//                     pattern: val[slot[k]] (+)= 0.5 (q_ij + q_ji), exactly symmetric
 //
 // The per-element arithmetic is three __host__ __device__ routines (fd_step, fd_perturb_one,
 // fd_quotient): the kernels and the *_host entries run the same operations in the same order,
@@ -229,6 +231,102 @@ k_fd_assemble(int64_t m, int64_t n, const int32_t *__restrict__ rowptr,
   }
 }
 
+// The symmetric assemble of a finite-difference HESSIAN (m = n, a structurally symmetric
+// pattern): entry (i, j) gets 0.5 * (q_ij + q_ji), q_ij the quotient k_fd_assemble would write at
+// (i, j) and q_ji the one it would write at (j, i) -- both read straight from the planes, so
+// there is no second pass and no transposition table.  Same launch shape as k_fd_assemble (one
+// workgroup per SpMV row tile, entries strided over the lanes, the row by bisection of the LDS
+// copy of the tile's rowptr slice, the loads of one dependency level issued for the lane's batch
+// before the next level uses them); an entry gathers twice as much, so a batch is 4 entries.
+//
+// Chunks of groups [g_lo, g_hi): a launch adds 0.5 * q_ij where g(j) is in range and 0.5 * q_ji
+// where g(i) is.  Scaling by 0.5 is exact (barring underflow) and the two-term sum commutative,
+// so 0.5 * q_ij + 0.5 * q_ji carries the bits of 0.5 * (q_ij + q_ji) whichever chunk brings
+// which half: chunked results equal single-launch results bit for bit.  An entry is FRESH in
+// the launch whose range holds min(g(i), g(j)) (chunks ascend): a fresh entry is written unless
+// `accumulate`, any other is added to.  `slot` (NULL: k) places entry k in a value array on a
+// larger pattern; a launch touches each slot once, so no atomics.
+template <int METHOD>
+__global__ void __launch_bounds__(IPX_BLOCK)
+k_fd_assemble_sym(int64_t n, const int32_t *__restrict__ rowptr,
+                  const int32_t *__restrict__ colidx, const int32_t *__restrict__ tiles,
+                  int ntiles, const int32_t *__restrict__ groups, int g_lo, int g_hi,
+                  const double *__restrict__ f0, const double *__restrict__ F1,
+                  const double *__restrict__ F2, const double *__restrict__ dx,
+                  const unsigned char *__restrict__ one_sided, const int32_t *__restrict__ slot,
+                  int accumulate, double *__restrict__ val) {
+  __shared__ int rp[TILE_ROWS + 1];
+  const int tile = ipx_xcd_item(blockIdx.x, ntiles);
+  if (tile < 0) return;
+  const int r0 = tiles[tile], r1 = tiles[tile + 1];
+  const int s = tiles[ntiles + 1 + tile], e = tiles[ntiles + 2 + tile];
+  const int nrows = r1 - r0;
+  if (e <= s || nrows <= 0) return;
+  const bool staged = nrows <= TILE_ROWS;          // (uniform over the workgroup)
+  if (staged) {
+    for (int i = threadIdx.x; i <= nrows; i += IPX_BLOCK) rp[i] = rowptr[r0 + i];
+    __syncthreads();
+  }
+  const int ng = g_hi - g_lo;
+  constexpr int U = 4;
+  for (int base = s + (int)threadIdx.x; base < e; base += U * IPX_BLOCK) {
+    int c[U], row[U], at[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = min(base + u * IPX_BLOCK, e - 1);
+      int cu = colidx[k];
+      c[u] = (cu >= 0 && (int64_t)cu < n) ? cu : 0;          // (a bad index reads column 0)
+      at[u] = slot ? slot[k] : k;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = min(base + u * IPX_BLOCK, e - 1);
+      int lo = 0, hi = nrows;                      // rowptr[r0 + lo] <= k < rowptr[r0 + hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        const int v = staged ? rp[mid] : rowptr[r0 + mid];
+        if (v <= k) lo = mid; else hi = mid;
+      }
+      row[u] = r0 + lo;
+    }
+    int gc[U], gr[U];                              // group of the column / of the row, - g_lo
+    double dc[U], dr[U], fr[U], fc[U];
+    unsigned char oc[U], orow[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      gc[u] = groups[c[u]] - g_lo;
+      gr[u] = groups[row[u]] - g_lo;
+      dc[u] = dx[c[u]];
+      dr[u] = dx[row[u]];
+      oc[u] = (METHOD == FD_3POINT) ? one_sided[c[u]] : 0;
+      orow[u] = (METHOD == FD_3POINT) ? one_sided[row[u]] : 0;
+      fr[u] = (METHOD == FD_CS) ? 0.0 : f0[row[u]];
+      fc[u] = (METHOD == FD_CS) ? 0.0 : f0[c[u]];
+    }
+    double a1[U], a2[U], b1[U], b2[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t pa = (gc[u] >= 0 && gc[u] < ng) ? (int64_t)gc[u] * n + row[u] : 0;
+      const int64_t pb = (gr[u] >= 0 && gr[u] < ng) ? (int64_t)gr[u] * n + c[u] : 0;
+      a1[u] = F1[pa];
+      b1[u] = F1[pb];
+      a2[u] = (METHOD == FD_3POINT) ? F2[pa] : 0.0;
+      b2[u] = (METHOD == FD_3POINT) ? F2[pb] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = base + u * IPX_BLOCK;
+      const bool ina = gc[u] >= 0 && gc[u] < ng, inb = gr[u] >= 0 && gr[u] < ng;
+      if (k >= e || !(ina || inb)) continue;
+      const double qa = 0.5 * fd_quotient(METHOD, oc[u], fr[u], a1[u], a2[u], dc[u]);
+      const double qb = 0.5 * fd_quotient(METHOD, orow[u], fc[u], b1[u], b2[u], dr[u]);
+      const double add = (ina && inb) ? qa + qb : (ina ? qa : qb);
+      const bool fresh = gc[u] >= 0 && gr[u] >= 0;
+      val[at[u]] = (fresh && !accumulate) ? add : val[at[u]] + add;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -321,6 +419,68 @@ void ipx_fd_assemble_host(int64_t m, int64_t n, const int32_t *rowptr, const int
       val[k] = fd_quotient(method, (method == FD_3POINT) ? one_sided[c] : 0,
                            (method == FD_CS) ? 0.0 : f0[i], F1[at],
                            (method == FD_3POINT) ? F2[at] : 0.0, dx[c]);
+    }
+}
+
+int ipx_fd_assemble_sym(int64_t n, const int32_t *rowptr, const int32_t *colidx,
+                        const int32_t *tiles, int32_t ntiles, int32_t method,
+                        const int32_t *groups, int32_t g_lo, int32_t g_hi, const double *f0,
+                        const double *F1, const double *F2, const double *dx,
+                        const unsigned char *one_sided, const int32_t *slot, int32_t accumulate,
+                        double *val, void *stream) {
+  if (n < 0 || ntiles < 0 || method < FD_2POINT || method > FD_CS || g_lo < 0 || g_hi < g_lo ||
+      n > INT32_MAX)
+    return IPX_EINVAL;
+  if (n == 0 || ntiles == 0 || g_hi == g_lo) return IPX_OK;
+  if (!rowptr || !colidx || !tiles || !groups || !F1 || !dx || !val ||
+      (method != FD_CS && !f0) || (method == FD_3POINT && (!F2 || !one_sided)))
+    return IPX_EINVAL;
+  const dim3 grid(ipx_xcd_grid(ntiles)), block(IPX_BLOCK);
+  const hipStream_t st = (hipStream_t)stream;
+  if (method == FD_2POINT)
+    hipLaunchKernelGGL(k_fd_assemble_sym<FD_2POINT>, grid, block, 0, st, n, rowptr, colidx, tiles,
+                       (int)ntiles, groups, (int)g_lo, (int)g_hi, f0, F1, F2, dx, one_sided, slot,
+                       (int)accumulate, val);
+  else if (method == FD_3POINT)
+    hipLaunchKernelGGL(k_fd_assemble_sym<FD_3POINT>, grid, block, 0, st, n, rowptr, colidx, tiles,
+                       (int)ntiles, groups, (int)g_lo, (int)g_hi, f0, F1, F2, dx, one_sided, slot,
+                       (int)accumulate, val);
+  else
+    hipLaunchKernelGGL(k_fd_assemble_sym<FD_CS>, grid, block, 0, st, n, rowptr, colidx, tiles,
+                       (int)ntiles, groups, (int)g_lo, (int)g_hi, f0, F1, F2, dx, one_sided, slot,
+                       (int)accumulate, val);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+void ipx_fd_assemble_sym_host(int64_t n, const int32_t *rowptr, const int32_t *colidx,
+                              int32_t method, const int32_t *groups, int32_t g_lo, int32_t g_hi,
+                              const double *f0, const double *F1, const double *F2,
+                              const double *dx, const unsigned char *one_sided,
+                              const int32_t *slot, int32_t accumulate, double *val) {
+  for (int64_t i = 0; i < n; ++i)
+    for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      const int32_t c = colidx[k];
+      if (c < 0 || c >= n) continue;
+      const int32_t gc = groups[c] - g_lo, gr = groups[i] - g_lo, ng = g_hi - g_lo;
+      const bool ina = gc >= 0 && gc < ng, inb = gr >= 0 && gr < ng;
+      if (!(ina || inb)) continue;
+      const bool three = method == FD_3POINT, cs = method == FD_CS;
+      double qa = 0.0, qb = 0.0;
+      if (ina) {
+        const int64_t pa = (int64_t)gc * n + i;
+        qa = 0.5 * fd_quotient(method, three ? one_sided[c] : 0, cs ? 0.0 : f0[i], F1[pa],
+                               three ? F2[pa] : 0.0, dx[c]);
+      }
+      if (inb) {
+        const int64_t pb = (int64_t)gr * n + c;
+        qb = 0.5 * fd_quotient(method, three ? one_sided[i] : 0, cs ? 0.0 : f0[c], F1[pb],
+                               three ? F2[pb] : 0.0, dx[i]);
+      }
+      const double add = (ina && inb) ? qa + qb : (ina ? qa : qb);
+      const bool fresh = gc >= 0 && gr >= 0;
+      const int64_t at = slot ? slot[k] : k;
+      val[at] = (fresh && !accumulate) ? add : val[at] + add;
     }
 }
 

@@ -9,6 +9,7 @@ loudly when the library or a HIP device is missing.
 from .minimize import minimize_constrained
 from .constraints import NonlinearConstraint, LinearConstraint, BoxConstraint
 from .quasi_newton import LBFGS, LSR1
+from .fd_hessian import SparseFD
 
 __all__ = ['minimize_constrained', 'NonlinearConstraint', 'LinearConstraint',
-           'BoxConstraint', 'LBFGS', 'LSR1']
+           'BoxConstraint', 'LBFGS', 'LSR1', 'SparseFD']

@@ -132,6 +132,8 @@ _SIGNATURES = {
     "ipx_fd_perturb": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble": [_I64, _I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P,
                         _P, _P],
+    "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                            _I32, _P, _P],
 }
 _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_launch_count": _c.c_longlong, "ipx_read_count": _c.c_longlong,
@@ -144,7 +146,8 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_sqp_radius_host": None, "ipx_sqp_box_sphere_host": None,
              "ipx_lowrank_state_doubles": _I64, "ipx_lowrank_part_doubles": _I64,
              "ipx_lowrank_middle_host": None, "ipx_fd_steps_host": None,
-             "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None}
+             "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None,
+             "ipx_fd_assemble_sym_host": None}
 _EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
                    "ipx_dense_padded": [_I64], "ipx_gram_ws_doubles": [_I64, _I32],
                    "ipx_peer_create": [_I32, _I32, _I64],
@@ -159,7 +162,9 @@ _EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy"
                    "ipx_fd_steps_host": [_I64, _I32, _F64, _P, _P, _P, _P, _P, _P],
                    "ipx_fd_perturb_host": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
                    "ipx_fd_assemble_host": [_I64, _I64, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P,
-                                            _P, _P, _P]}
+                                            _P, _P, _P],
+                   "ipx_fd_assemble_sym_host": [_I64, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P,
+                                                _P, _P, _I32, _P]}
 
 _lib = None
 

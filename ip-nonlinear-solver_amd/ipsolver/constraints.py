@@ -11,6 +11,7 @@ import numpy as np
 import scipy.sparse as sps
 
 from .fd import FiniteDifferenceOperator, FD_METHODS
+from .fd_hessian import SparseFD, FDTerm, Memo
 
 __all__ = ['NonlinearConstraint', 'LinearConstraint', 'BoxConstraint']
 
@@ -142,6 +143,10 @@ def check_fd_jacobian_arguments(jac, hess, sparsity, rel_step):
     if isinstance(jac, str):
         if jac not in FD_METHODS:
             raise ValueError("`jac` must be callable or one of %r, got %r" % (FD_METHODS, jac))
+        if isinstance(hess, SparseFD):
+            raise ValueError("hess=%r cannot be combined with a finite-difference `jac` (%r): it "
+                             "would difference a differenced Jacobian; pass a callable `jac`, or "
+                             "use the operator form hess='2-point' / '3-point'" % (hess, jac))
         if jac == 'cs' and isinstance(hess, str) and hess in FD_METHODS:
             raise ValueError("jac='cs' cannot be combined with a finite-difference `hess` (%r): "
                              "complex steps do not nest; pass a callable `hess`, None, or use "
@@ -211,6 +216,10 @@ class NonlinearConstraint(_Initialised):
         self.fun = lambda x: np.atleast_1d(self._fun(x))
         self.sparse_jacobian = bool(sparse_jacobian
                                     or (sparse_jacobian is None and sps.issparse(J0)))
+        if isinstance(self._hess, SparseFD):
+            # the Jacobian the solver evaluated at the Hessian's point is the f0 of the difference
+            self.fd_hessian = FDTerm(self._hess, x0.size, "constraint")
+            user_jac = memo = Memo(user_jac, x0, J0)
         if self.sparse_jacobian:
             self.jac = lambda x: canonical_csr(user_jac(x))
             self.J0 = canonical_csr(J0)
@@ -229,6 +238,13 @@ class NonlinearConstraint(_Initialised):
             def fd_hess(x, v):          # d/dx [J(x)' v] by differences (:136-146)
                 return FiniteDifferenceOperator(lambda y: jac(y).T.dot(v), x, method)
             self.hess = fd_hess
+        elif isinstance(self._hess, SparseFD):
+            term, raw_jac = self.fd_hessian, memo.fun
+
+            def sparse_fd_hess(x, v):   # the same difference, grouped, as one CSR term
+                return term.request(lambda y: raw_jac(y).T.dot(v),
+                                    lambda: memo.lookup(x).T.dot(v))
+            self.hess = sparse_fd_hess
         else:
             self.hess = self._hess
         self._finish(x0, f0)

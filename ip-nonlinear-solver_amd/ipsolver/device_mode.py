@@ -279,8 +279,18 @@ class _DeviceConstraint:
                 # the plan -- ONE CSRPattern for the run -- is built here, the first evaluation
                 # uses the value the constraint already has at x0
                 ujac = self.fd_jacobian = _DeviceFDJacobian(user, ufun, n, len(f0), x0, f0)
+            from .fd_hessian import SparseFD, FDTerm, DeviceMemo
+            if isinstance(uhess, SparseFD):
+                # the grouped difference of x -> J(x)' v as one CSR term; the Jacobian the solver
+                # evaluated at the Hessian's point is the f0 of the difference
+                term = self.fd_hessian = FDTerm(uhess, n, "constraint", device_mode=True)
+                raw_jac, ujac = ujac, DeviceMemo(ujac, _check_jac)
             self.jac = lambda x: _check_jac(ujac(x.t))
-            if uhess in ('2-point', '3-point', 'cs'):
+            if isinstance(uhess, SparseFD):
+                self.hess = lambda x, v: term.request(
+                    lambda xt: _check_jac(raw_jac(xt)).T.dot(v),
+                    lambda: ujac.lookup(x.t).T.dot(v))
+            elif uhess in ('2-point', '3-point', 'cs'):
                 # d/dx [J(x)' v] by differences (reference _constraints.py:136-146), on the device
                 from .fd import DeviceFiniteDifferenceOperator
                 self.hess = lambda x, v: DeviceFiniteDifferenceOperator(
@@ -543,7 +553,8 @@ def _as_term(h):
     """Normalise a Hessian callback's return value to a device term."""
     from .dense import DeviceDense
     from .operators import DeviceHessian
-    if h is None or isinstance(h, (DeviceCSR, DVec, DeviceHessian, DeviceDense)) \
+    from .fd_hessian import FDRequest
+    if h is None or isinstance(h, (DeviceCSR, DVec, DeviceHessian, DeviceDense, FDRequest)) \
             or getattr(h, "device_operator", False):
         return h
     if torch.is_tensor(h) and h.dim() == 1:
@@ -579,6 +590,9 @@ def _dense_term(t):
 
 def lagrangian_hessian(canonical, hess):
     """Device twin of canonical.lagrangian_hessian (terms in hess_list order)."""
+    from .fd_hessian import LagrangianFDHessian
+    fd_lagr = LagrangianFDHessian()     # (SparseFD terms: ONE DeviceCSR on one pattern)
+
     def lagr_hess(x, v_eq=None, v_ineq=None):
         terms = []
         if hess is not None:
@@ -586,7 +600,7 @@ def lagrangian_hessian(canonical, hess):
         if canonical.hess is not None:
             terms.extend(canonical.hess(x, v_eq if v_eq is not None else DVec.zeros(0),
                                         v_ineq if v_ineq is not None else DVec.zeros(0)))
-        return HessianSum(len(x), [t for t in terms if t is not None])
+        return HessianSum(len(x), fd_lagr.resolve([t for t in terms if t is not None], x))
     return lagr_hess
 
 

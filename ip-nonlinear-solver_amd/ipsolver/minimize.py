@@ -18,10 +18,12 @@ from scipy.optimize import OptimizeResult
 
 from . import backend as _backend
 from .barrier import tr_interior_point
-from .canonical import lagrangian_hessian, to_canonical, empty_canonical_constraint
+from .canonical import (lagrangian_hessian, to_canonical, empty_canonical_constraint,
+                        HessianSum)
 from .constraints import (NonlinearConstraint, LinearConstraint, BoxConstraint, wrap_hessian)
 from .fd import FiniteDifferenceOperator, FD_METHODS
 from . import quasi_newton as _qn
+from . import fd_hessian as _fdh
 from .sqp import equality_constrained_sqp
 
 __all__ = ['minimize_constrained']
@@ -112,11 +114,17 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
     from . import device_mode as dm
     if xp.name != "hip":
         raise RuntimeError("device-callback mode needs the HIP backend")
-    qn_memory = None
+    qn_memory = fd_objective = None
     if _qn.is_strategy(hess):
         # the gradient at every accepted point is the one the solver evaluated there
         grad = _qn.DeviceGradientMemo(grad)
         hess, qn_memory = _qn.device_hessian(hess, grad, x0.numel())
+    elif _fdh.is_sparse_fd(hess):
+        # grouped differences of the device gradient into one CSR term (fd_hessian.py); the
+        # gradient the solver evaluated at the Hessian's point is the f0 of the difference
+        raw_grad, grad = grad, _qn.DeviceGradientMemo(grad)
+        fd_objective = _fdh.FDTerm(hess, x0.numel(), "objective", device_mode=True)
+        hess = lambda xt, _m=grad: fd_objective.request(raw_grad, lambda: _m.lookup(xt))
     elif hess in FD_METHODS:           # N4: differences of the device gradient callback
         from .fd import DeviceFiniteDifferenceOperator
         fd_method = hess
@@ -168,6 +176,7 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
     if qn_memory is not None:
         result.hess_updates, result.hess_skipped = qn_memory.counts()
     _report_fd_jacobian_calls(result, canon.parts)
+    _fdh.report_calls(result, fd_objective, canon.parts)
     for k in _VECTOR_FIELDS:
         if k in result and hasattr(result[k], "t"):
             result[k] = result[k].t
@@ -420,6 +429,17 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "
                                   "differences ('2-point', '3-point', 'cs')" % (hess,))
+    fd_hess = [h for h in [hess] + [c._hess for c in _constraint_list(constraints)
+                                    if isinstance(c, NonlinearConstraint)]
+               if _fdh.is_sparse_fd(h)]
+    if fd_hess and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("hess=%r: sparse finite-difference Hessians are not available "
+                                  "on the row-sharded backend; pass an exact Hessian or the "
+                                  "operator form ('2-point', '3-point', 'cs')" % (fd_hess[0],))
+    if _fdh.is_sparse_fd(hess) and constant_hessian:
+        raise ValueError("options={'constant_hessian': True} cannot be combined with hess=%r: a "
+                         "differenced Hessian is evaluated at every accepted point; pass a "
+                         "callable `hess` with constant_hessian, or drop the option" % (hess,))
     fd_jac = [c._jac for c in _constraint_list(constraints)
               if isinstance(c, NonlinearConstraint) and isinstance(c._jac, str)]
     if fd_jac and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
@@ -448,9 +468,10 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
 
     def plain_grad(x):
         return np.atleast_1d(grad(x))
-    grad_wrapped = (_Memoize(plain_grad, x0, g0) if hess in FD_METHODS or _qn.is_strategy(hess)
+    grad_wrapped = (_Memoize(plain_grad, x0, g0)
+                    if hess in FD_METHODS or _qn.is_strategy(hess) or _fdh.is_sparse_fd(hess)
                     else plain_grad)
-    qn_memory = None
+    qn_memory = fd_objective = None
 
     if callable(hess) and constant_hessian:
         # ADDITIVE option (the reference has none; its signature is unchanged): the objective's
@@ -472,6 +493,11 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
             return FiniteDifferenceOperator(grad_wrapped, x, hess)
     elif _qn.is_strategy(hess):
         hess_wrapped, qn_memory = _qn.host_hessian(hess, grad_wrapped, n_vars)
+    elif _fdh.is_sparse_fd(hess):
+        fd_objective = _fdh.FDTerm(hess, n_vars, "objective")
+
+        def hess_wrapped(x):
+            return fd_objective.request(plain_grad, lambda: grad_wrapped(x))
     else:
         hess_wrapped = hess
 
@@ -483,6 +509,13 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     constr = (empty_canonical_constraint(x0, n_vars, sparse_jacobian) if len(copied) == 0
               else to_canonical(copied))
     host_lagr_hess = lagrangian_hessian(constr, hess_wrapped)
+    if fd_hess:
+        # the differenced terms become ONE DeviceCSR on one pattern, the operator's csr term
+        plain_lagr_hess, fd_lagr = host_lagr_hess, _fdh.LagrangianFDHessian(host_callbacks=True)
+
+        def host_lagr_hess(x, *v):
+            terms = plain_lagr_hess(x, *v)
+            return HessianSum(n_vars, fd_lagr.resolve(terms.flat_terms(), x))
     if shard:
         from .constraints import _is_operator
         op_hess = hess in FD_METHODS or (callable(hess) and _is_operator(hess(x0))) \
@@ -595,6 +628,7 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     if qn_memory is not None:
         result.hess_updates, result.hess_skipped = qn_memory.counts()
     _report_fd_jacobian_calls(result, copied)
+    _fdh.report_calls(result, fd_objective, copied)
     for k in _VECTOR_FIELDS:
         if k in result:
             result[k] = xp.tohost(result[k])
