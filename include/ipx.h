@@ -776,6 +776,27 @@ int ipx_lowrank_apply(int64_t n, int32_t mem, const double *W, const double *sta
  * dots = (s'W [2 mem], y'W [2 mem], s's, s'y, y'y): the same arithmetic as the kernel */
 void ipx_lowrank_middle_host(int32_t kind, int32_t mem, double init_scale, double threshold,
                              double *state, const double *dots);
+/* The y of a pair when the memory also approximates constraint Hessians (one memory for the
+ * Lagrangian terms declared with a strategy, ipsolver/quasi_newton.py LagrangianQN): for every
+ * variable j
+ *   y[j] = ((accumulate ? y[j] : 0) + (base_new ? base_new[j] - base_old[j] : 0))
+ *          + sum_k v[t_rowidx[k]] * (val_new[t_perm[k]] - val_old[t_perm[k]])
+ * k over row j of the TRANSPOSED pattern of an m x n Jacobian (n rows, nnz entries; t_perm: the
+ * position of entry k in the Jacobian's own value array; t_tiles: ipx_csr_tiles_host of
+ * t_rowptr) in stored order, the sum started from 0, plain operations.  val_new / val_old: the
+ * Jacobian's values at the new and the previous point, on one pattern; base_new / base_old: both
+ * or neither (the objective's gradients).  One launch, no atomics; rows longer than a tile keep
+ * the same order.  The _host twin runs the same per-row routine on host arrays (and checks the
+ * index arrays: IPX_EINVAL). */
+int ipx_csr_tdiff_dot(int64_t n, int64_t m, int64_t nnz, const int32_t *t_rowptr,
+                      const int32_t *t_rowidx, const int64_t *t_perm, const int32_t *t_tiles,
+                      int32_t t_ntiles, const double *val_new, const double *val_old,
+                      const double *v, const double *base_new, const double *base_old, double *y,
+                      int32_t accumulate, void *stream);
+int ipx_csr_tdiff_dot_host(int64_t n, int64_t m, int64_t nnz, const int32_t *t_rowptr,
+                           const int32_t *t_rowidx, const int64_t *t_perm, const double *val_new,
+                           const double *val_old, const double *v, const double *base_new,
+                           const double *base_old, double *y, int32_t accumulate);
 
 /* ---- sparse finite-difference Jacobians (csrc/fdjac.hip, ipsolver/fd_jacobian.py) ----
  * Curtis-Powell-Reid grouped differences of a constraint function on a fixed CSR pattern

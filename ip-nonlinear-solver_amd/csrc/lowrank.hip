@@ -22,6 +22,9 @@
 // The middle-matrix arithmetic is one __host__ __device__ routine (lr_middle): the device runs
 // it in one workgroup, ipx_lowrank_middle_host runs the same operations in the same order on
 // the host, so CPU tests pin the numbers.
+//
+// At the end of the file: ipx_csr_tdiff_dot, the y of a pair whose memory also approximates
+// constraint Hessians -- [g+ - g] + (J(x+) - J(x))' v in one launch per constraint.
 #include "ipx_common.h"
 #include <math.h>
 #include <string.h>
@@ -507,6 +510,176 @@ void ipx_lowrank_middle_host(int32_t kind, int32_t mem, double init_scale, doubl
   static thread_local LrShared S;
   memcpy(S.d, dots, sizeof(double) * (4 * mem + 3));
   lr_middle(S, state, kind, mem, init_scale, threshold, 0, 1);
+}
+
+}  // extern "C"
+
+// ---- the pair's y for constraint terms: y (+)= [g+ - g] + (J(x+) - J(x))' v -------------------
+//
+// One memory approximates the sum of the Lagrangian-Hessian terms declared with a strategy
+// (quasi_newton.LagrangianQN), so its y needs (J+ - J)' v of every such constraint.  J+ and J share
+// one CSR pattern; the kernel walks the TRANSPOSED pattern (CSRPattern.transpose: row j = column j
+// of J, its entries' rows in t_rowidx, their positions in J's value array in t_perm) and reads
+// both value arrays through the permutation -- no transposed value array is made.  Row j:
+//
+//     y[j] = ((accumulate ? y[j] : 0) + (base_new ? base_new[j] - base_old[j] : 0))
+//            + sum_k v[t_rowidx[k]] * (val_new[t_perm[k]] - val_old[t_perm[k]])
+//
+// the sum from 0 in stored order, plain operations (-ffp-contract=off).  The tiles are spmv.hip's:
+// a workgroup streams its tile's entries (lane i -> entry i), parks the terms in LDS, then one
+// lane per row adds its terms left to right.  A row longer than a tile has a tile of its own:
+// the workgroup stages it chunk by chunk and ONE lane carries the sum through the chunks, so every
+// row has the host routine's order whatever its length (no atomics, no tree).
+//
+// Algorithmic HBM bytes: 36 per entry (row index 4, permutation 8, two values 16, the gathered
+// v 8) + 4 (n + 1) row pointers + 8 n out (+ 8 n per base vector, + 8 n when accumulating).
+namespace {
+
+constexpr int TD_TILE_NNZ = IPX_SPMV_TILE_NNZ;
+
+__host__ __device__ inline double lr_tdiff_mul(double v, double a_new, double a_old) {
+  return v * (a_new - a_old);
+}
+
+__host__ __device__ inline double lr_tdiff_term(int64_t k, const int32_t *ri, const int64_t *perm,
+                                                const double *vn, const double *vo,
+                                                const double *v) {
+  const int64_t p = perm[k];
+  return lr_tdiff_mul(v[ri[k]], vn[p], vo[p]);
+}
+
+// sum + the terms [a, b) of a row, left to right; `terms` (staged by the caller: term k at
+// terms[k - off]) or, NULL, straight from the arrays
+__host__ __device__ inline double lr_tdiff_sum(double sum, int64_t a, int64_t b,
+                                               const double *terms, int64_t off,
+                                               const int32_t *ri, const int64_t *perm,
+                                               const double *vn, const double *vo,
+                                               const double *v) {
+  for (int64_t k = a; k < b; ++k)
+    sum = sum + (terms ? terms[k - off] : lr_tdiff_term(k, ri, perm, vn, vo, v));
+  return sum;
+}
+
+// the per-row routine: row j of the transposed pattern from its finished sum
+__host__ __device__ inline double lr_tdiff_row(int64_t j, double sum, const double *base_new,
+                                               const double *base_old, const double *y,
+                                               int accumulate) {
+  const double head = accumulate ? y[j] : 0.0;
+  const double base = base_new ? base_new[j] - base_old[j] : 0.0;
+  return (head + base) + sum;
+}
+
+__global__ void __launch_bounds__(IPX_BLOCK)
+k_csr_tdiff_dot(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ rowidx,
+                const int64_t *__restrict__ perm, const int32_t *__restrict__ tiles, int ntiles,
+                const double *__restrict__ vn, const double *__restrict__ vo,
+                const double *__restrict__ v, const double *__restrict__ base_new,
+                const double *__restrict__ base_old, double *y, int accumulate) {
+  __shared__ double terms[TD_TILE_NNZ];
+  const int tile = ipx_xcd_item(blockIdx.x, ntiles);
+  if (tile < 0) return;
+  const int r0 = tiles[tile], r1 = tiles[tile + 1];
+  const int s = tiles[ntiles + 1 + tile], e = tiles[ntiles + 2 + tile];
+  const int tid = threadIdx.x;
+  if (e - s <= TD_TILE_NNZ) {
+    if (e > s) {
+      // every load of a lane issued before the first use: indices, then the three gathers
+      constexpr int U = TD_TILE_NNZ / IPX_BLOCK;
+      int ri[U];
+      int64_t p[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = min(s + tid + u * IPX_BLOCK, e - 1);
+        ri[u] = rowidx[k];
+        p[u] = perm[k];
+      }
+      double mv[U], a[U], b[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        mv[u] = v[ri[u]];
+        a[u] = vn[p[u]];
+        b[u] = vo[p[u]];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = s + tid + u * IPX_BLOCK;
+        if (k < e) terms[k - s] = lr_tdiff_mul(mv[u], a[u], b[u]);
+      }
+    }
+    __syncthreads();
+    for (int r = r0 + tid; r < r1; r += IPX_BLOCK) {
+      const double sum = lr_tdiff_sum(0.0, rowptr[r], rowptr[r + 1], terms, s, nullptr, nullptr,
+                                      nullptr, nullptr, nullptr);
+      y[r] = lr_tdiff_row(r, sum, base_new, base_old, y, accumulate);
+    }
+    return;
+  }
+  // a tile is over-long only when it is a single very long row
+  for (int r = r0; r < r1; ++r) {
+    const int a = rowptr[r], b = rowptr[r + 1];
+    double sum = 0.0;
+    for (int c = a; c < b; c += TD_TILE_NNZ) {
+      const int ce = min(c + TD_TILE_NNZ, b);
+      for (int k = c + tid; k < ce; k += IPX_BLOCK)
+        terms[k - c] = lr_tdiff_term(k, rowidx, perm, vn, vo, v);
+      __syncthreads();
+      if (tid == 0)
+        sum = lr_tdiff_sum(sum, c, ce, terms, c, nullptr, nullptr, nullptr, nullptr, nullptr);
+      __syncthreads();
+    }
+    if (tid == 0) y[r] = lr_tdiff_row(r, sum, base_new, base_old, y, accumulate);
+  }
+}
+
+bool tdiff_args_ok(int64_t n, int64_t m, int64_t nnz, const void *rowptr, const void *rowidx,
+                   const void *perm, const void *vn, const void *vo, const void *v,
+                   const void *base_new, const void *base_old, const void *y) {
+  if (n < 0 || m < 0 || nnz < 0 || nnz > INT32_MAX || n > INT32_MAX || m > INT32_MAX) return false;
+  if ((base_new == nullptr) != (base_old == nullptr)) return false;
+  if (n > 0 && (!rowptr || !y)) return false;
+  if (nnz > 0 && (m == 0 || !rowidx || !perm || !vn || !vo || !v)) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ipx_csr_tdiff_dot(int64_t n, int64_t m, int64_t nnz, const int32_t *t_rowptr,
+                      const int32_t *t_rowidx, const int64_t *t_perm, const int32_t *t_tiles,
+                      int32_t t_ntiles, const double *val_new, const double *val_old,
+                      const double *v, const double *base_new, const double *base_old, double *y,
+                      int32_t accumulate, void *stream) {
+  if (!tdiff_args_ok(n, m, nnz, t_rowptr, t_rowidx, t_perm, val_new, val_old, v, base_new,
+                     base_old, y) || t_ntiles < 0 || (n > 0 && (!t_tiles || t_ntiles < 1)))
+    return IPX_EINVAL;
+  if (n == 0) return IPX_OK;
+  hipLaunchKernelGGL(k_csr_tdiff_dot, dim3(ipx_xcd_grid(t_ntiles)), dim3(IPX_BLOCK), 0,
+                     (hipStream_t)stream, t_rowptr, t_rowidx, t_perm, t_tiles, (int)t_ntiles,
+                     val_new, val_old, v, base_new, base_old, y, (int)accumulate);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+int ipx_csr_tdiff_dot_host(int64_t n, int64_t m, int64_t nnz, const int32_t *t_rowptr,
+                           const int32_t *t_rowidx, const int64_t *t_perm, const double *val_new,
+                           const double *val_old, const double *v, const double *base_new,
+                           const double *base_old, double *y, int32_t accumulate) {
+  if (!tdiff_args_ok(n, m, nnz, t_rowptr, t_rowidx, t_perm, val_new, val_old, v, base_new,
+                     base_old, y))
+    return IPX_EINVAL;
+  if (n > 0 && (t_rowptr[0] != 0 || t_rowptr[n] != nnz)) return IPX_EINVAL;
+  for (int64_t j = 0; j < n; ++j)
+    if (t_rowptr[j + 1] < t_rowptr[j]) return IPX_EINVAL;
+  for (int64_t k = 0; k < nnz; ++k)
+    if (t_rowidx[k] < 0 || t_rowidx[k] >= m || t_perm[k] < 0 || t_perm[k] >= nnz)
+      return IPX_EINVAL;
+  for (int64_t j = 0; j < n; ++j) {
+    const double sum = lr_tdiff_sum(0.0, t_rowptr[j], t_rowptr[j + 1], nullptr, 0, t_rowidx,
+                                    t_perm, val_new, val_old, v);
+    y[j] = lr_tdiff_row(j, sum, base_new, base_old, y, accumulate);
+  }
+  return IPX_OK;
 }
 
 }  // extern "C"

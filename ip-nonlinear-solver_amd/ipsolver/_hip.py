@@ -128,6 +128,8 @@ _SIGNATURES = {
     "ipx_lowrank_grid": [_I64],
     "ipx_lowrank_update": [_I32, _I64, _I32, _F64, _F64, _P, _P, _P, _P, _P, _P],
     "ipx_lowrank_apply": [_I64, _I32, _P, _P, _P, _P, _I32, _P, _P],
+    "ipx_csr_tdiff_dot": [_I64, _I64, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _I32, _P],
+    "ipx_csr_tdiff_dot_host": [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32],
     "ipx_fd_steps": [_I64, _I32, _F64, _P, _P, _P, _P, _P, _P, _P],
     "ipx_fd_perturb": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble": [_I64, _I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P,

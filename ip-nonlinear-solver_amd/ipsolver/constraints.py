@@ -12,6 +12,7 @@ import scipy.sparse as sps
 
 from .fd import FiniteDifferenceOperator, FD_METHODS
 from .fd_hessian import SparseFD, FDTerm, Memo
+from . import quasi_newton as _qn
 
 __all__ = ['NonlinearConstraint', 'LinearConstraint', 'BoxConstraint']
 
@@ -190,6 +191,19 @@ class NonlinearConstraint(_Initialised):
     ``fun`` (``_numdiff.approx_derivative``; scipy's keyword names).  ``finite_diff_jac_sparsity``
     is a sparsity structure or ``(structure, groups)``; without it the difference is dense (n
     evaluations; refused in device-callback mode).
+
+    ``hess`` is a callable ``hess(x, v)``, None, '2-point' / '3-point' / 'cs' (the operator form:
+    differences of ``x -> J(x)' v`` inside every CG iteration), ``SparseFD(...)`` (the same
+    difference assembled into a CSR term once per accepted point) or a quasi-Newton strategy,
+    ``ipsolver.LBFGS(...)`` / ``ipsolver.LSR1(...)``, in both callback modes and with any
+    ``jac``.  With a strategy the constraint's curvature is a term of ONE limited-memory
+    approximation of the Lagrangian's Hessian (``quasi_newton.LagrangianQN``): its pair takes
+    ``(J(x+) - J(x))' v`` from the Jacobians the solver evaluates anyway -- no extra calls of
+    ``jac`` -- and the CG loops apply it as one low-rank term.  Every constraint with a strategy,
+    and the objective if ``minimize_constrained(hess=...)`` is one, must carry EQUAL strategies
+    (a ``ValueError`` otherwise).  The Lagrangian's Hessian is usually indefinite, so ``LSR1``
+    is the rule to prefer here; ``LBFGS`` skips every pair with ``s'y <= min_curvature ||s||
+    ||y||``.
     """
 
     def __init__(self, fun, kind, jac, hess='2-point', enforce_feasibility=False,
@@ -220,6 +234,11 @@ class NonlinearConstraint(_Initialised):
             # the Jacobian the solver evaluated at the Hessian's point is the f0 of the difference
             self.fd_hessian = FDTerm(self._hess, x0.size, "constraint")
             user_jac = memo = Memo(user_jac, x0, J0)
+        elif _qn.is_strategy(self._hess):
+            # a term of the Lagrangian's one quasi-Newton memory: its request carries the
+            # Jacobian the solver evaluated at the Hessian's point
+            self.qn_hessian = self._hess
+            user_jac = memo = Memo(user_jac, x0, J0, reuse=True)
         if self.sparse_jacobian:
             self.jac = lambda x: canonical_csr(user_jac(x))
             self.J0 = canonical_csr(J0)
@@ -245,6 +264,17 @@ class NonlinearConstraint(_Initialised):
                 return term.request(lambda y: raw_jac(y).T.dot(v),
                                     lambda: memo.lookup(x).T.dot(v))
             self.hess = sparse_fd_hess
+        elif _qn.is_strategy(self._hess):
+            n, sparse = x0.size, self.sparse_jacobian
+
+            def qn_hess(x, v):          # the Jacobian in the form ``self.jac`` gives it
+                J = memo.lookup(x)
+                if sparse:
+                    J = canonical_csr(J)
+                else:
+                    J = J.toarray() if sps.issparse(J) else np.atleast_2d(J)
+                return _qn.QNRequest(n, J=J, v=v)
+            self.hess = qn_hess
         else:
             self.hess = self._hess
         self._finish(x0, f0)

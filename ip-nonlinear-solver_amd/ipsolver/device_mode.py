@@ -280,13 +280,21 @@ class _DeviceConstraint:
                 # uses the value the constraint already has at x0
                 ujac = self.fd_jacobian = _DeviceFDJacobian(user, ufun, n, len(f0), x0, f0)
             from .fd_hessian import SparseFD, FDTerm, DeviceMemo
+            from . import quasi_newton as _qn
+            if _qn.is_strategy(uhess):
+                # a term of the Lagrangian's one quasi-Newton memory: its request carries the
+                # Jacobian the solver evaluated at the Hessian's point and the multipliers
+                self.qn_hessian = uhess
+                ujac = DeviceMemo(ujac, _check_jac, reuse=True)
             if isinstance(uhess, SparseFD):
                 # the grouped difference of x -> J(x)' v as one CSR term; the Jacobian the solver
                 # evaluated at the Hessian's point is the f0 of the difference
                 term = self.fd_hessian = FDTerm(uhess, n, "constraint", device_mode=True)
                 raw_jac, ujac = ujac, DeviceMemo(ujac, _check_jac)
             self.jac = lambda x: _check_jac(ujac(x.t))
-            if isinstance(uhess, SparseFD):
+            if _qn.is_strategy(uhess):
+                self.hess = lambda x, v: _qn.QNRequest(n, J=ujac.lookup(x.t), v=v)
+            elif isinstance(uhess, SparseFD):
                 self.hess = lambda x, v: term.request(
                     lambda xt: _check_jac(raw_jac(xt)).T.dot(v),
                     lambda: ujac.lookup(x.t).T.dot(v))
@@ -554,7 +562,9 @@ def _as_term(h):
     from .dense import DeviceDense
     from .operators import DeviceHessian
     from .fd_hessian import FDRequest
-    if h is None or isinstance(h, (DeviceCSR, DVec, DeviceHessian, DeviceDense, FDRequest)) \
+    from .quasi_newton import QNRequest
+    if h is None or isinstance(h, (DeviceCSR, DVec, DeviceHessian, DeviceDense, FDRequest,
+                                   QNRequest)) \
             or getattr(h, "device_operator", False):
         return h
     if torch.is_tensor(h) and h.dim() == 1:
@@ -588,8 +598,9 @@ def _dense_term(t):
     return hit[1]
 
 
-def lagrangian_hessian(canonical, hess):
-    """Device twin of canonical.lagrangian_hessian (terms in hess_list order)."""
+def lagrangian_hessian(canonical, hess, qn_lagr=None):
+    """Device twin of canonical.lagrangian_hessian (terms in hess_list order).  ``qn_lagr``
+    (``quasi_newton.LagrangianQN``): the memory the quasi-Newton requests resolve into."""
     from .fd_hessian import LagrangianFDHessian
     fd_lagr = LagrangianFDHessian()     # (SparseFD terms: ONE DeviceCSR on one pattern)
 
@@ -600,7 +611,10 @@ def lagrangian_hessian(canonical, hess):
         if canonical.hess is not None:
             terms.extend(canonical.hess(x, v_eq if v_eq is not None else DVec.zeros(0),
                                         v_ineq if v_ineq is not None else DVec.zeros(0)))
-        return HessianSum(len(x), fd_lagr.resolve([t for t in terms if t is not None], x))
+        terms = fd_lagr.resolve([t for t in terms if t is not None], x)
+        if qn_lagr is not None:
+            terms = qn_lagr.resolve(terms, x)
+        return HessianSum(len(x), terms)
     return lagr_hess
 
 

@@ -115,7 +115,15 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
     if xp.name != "hip":
         raise RuntimeError("device-callback mode needs the HIP backend")
     qn_memory = fd_objective = None
-    if _qn.is_strategy(hess):
+    qn_terms = _qn.participating(hess, _constraint_list(constraints))
+    if qn_terms:
+        # some constraint carries a strategy: ONE memory for the Lagrangian's participating
+        # terms (quasi_newton.LagrangianQN); a strategy objective hands it its memoised gradient
+        qn_memory = _qn.LagrangianQN(qn_terms[0], x0.numel())
+    if qn_terms and _qn.is_strategy(hess):
+        grad = _qn.DeviceGradientMemo(grad)
+        hess = lambda xt, _m=grad, _n=x0.numel(): _qn.QNRequest(_n, g=_m.lookup(xt))
+    elif _qn.is_strategy(hess):
         # the gradient at every accepted point is the one the solver evaluated there
         grad = _qn.DeviceGradientMemo(grad)
         hess, qn_memory = _qn.device_hessian(hess, grad, x0.numel())
@@ -137,7 +145,8 @@ def _minimize_device(fun, x0, grad, hess, constraints, method, xtol, gtol, optio
         constraints = [constraints]
     canon = dm.DeviceCanonical(list(constraints), x0_dev)
     x0_dev = canon.x0
-    lagr = dm.lagrangian_hessian(canon, hess if callable(hess) else None)
+    lagr = dm.lagrangian_hessian(canon, hess if callable(hess) else None,
+                                 qn_memory if qn_terms else None)
 
     state = OptimizeResult(niter=0, nfev=1, ngev=1, ncev=1, njev=1, nhev=0, cg_niter=0,
                            cg_info={})
@@ -429,6 +438,17 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "
                                   "differences ('2-point', '3-point', 'cs')" % (hess,))
+    qn_terms = _qn.participating(hess, _constraint_list(constraints))
+    if qn_terms and constant_hessian:
+        raise ValueError("options={'constant_hessian': True} cannot be combined with a "
+                         "quasi-Newton constraint hess (%r): its approximation changes at every "
+                         "step; drop the option, or give the constraints Hessian callbacks"
+                         % (qn_terms[-1],))
+    if qn_terms and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("NonlinearConstraint(hess=%r): quasi-Newton Hessians are not "
+                                  "available on the row-sharded backend; pass an exact Hessian "
+                                  "or finite differences ('2-point', '3-point', 'cs')"
+                                  % (qn_terms[-1],))
     fd_hess = [h for h in [hess] + [c._hess for c in _constraint_list(constraints)
                                     if isinstance(c, NonlinearConstraint)]
                if _fdh.is_sparse_fd(h)]
@@ -491,6 +511,11 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     elif hess in FD_METHODS:
         def hess_wrapped(x):
             return FiniteDifferenceOperator(grad_wrapped, x, hess)
+    elif _qn.is_strategy(hess) and qn_terms:
+        # a constraint carries a strategy too: the objective hands the Lagrangian's ONE memory
+        # its memoised gradient and no longer updates by itself
+        def hess_wrapped(x):
+            return _qn.QNRequest(n_vars, g=grad_wrapped(x))
     elif _qn.is_strategy(hess):
         hess_wrapped, qn_memory = _qn.host_hessian(hess, grad_wrapped, n_vars)
     elif _fdh.is_sparse_fd(hess):
@@ -516,6 +541,14 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
         def host_lagr_hess(x, *v):
             terms = plain_lagr_hess(x, *v)
             return HessianSum(n_vars, fd_lagr.resolve(terms.flat_terms(), x))
+    if qn_terms:
+        # the participating terms become the ONE low-rank term of the Lagrangian's memory
+        inner_lagr_hess = host_lagr_hess
+        qn_memory = _qn.LagrangianQN(qn_terms[0], n_vars, host_callbacks=True)
+
+        def host_lagr_hess(x, *v):
+            terms = inner_lagr_hess(x, *v)
+            return HessianSum(n_vars, qn_memory.resolve(terms.flat_terms(), x))
     if shard:
         from .constraints import _is_operator
         op_hess = hess in FD_METHODS or (callable(hess) and _is_operator(hess(x0))) \

@@ -1,5 +1,6 @@
-"""Limited-memory quasi-Newton approximations of the objective's Hessian: ``hess=LBFGS()`` or
-``hess=LSR1()`` in ``minimize_constrained``, for problems that have no Hessian callback.
+"""Limited-memory quasi-Newton approximations of Hessians the user has no callback for:
+``hess=LBFGS()`` or ``hess=LSR1()`` in ``minimize_constrained`` (the objective) and in
+``NonlinearConstraint(fun, kind, jac, hess=...)`` (a constraint).
 
 The objects hold parameters only.  Every solve starts from an empty memory (``_Memory``), so two
 solves with the same object give the same bits.  They are deliberately not callable: the
@@ -10,8 +11,18 @@ Both rules keep the compact form ``B = sigma I + W C W'`` with ``W = [S Y]`` on 
 signs are folded into C, and a product is ``B p = sigma p + W (C (W'p))`` -- two HBM-bound
 passes over W, no host involvement.  An update is three launches and reads nothing back.
 
-Only the objective is approximated: constraint Hessians still come from their callbacks, from
-finite differences or are absent, exactly as without a strategy.
+A strategy on the objective alone approximates the objective's Hessian; constraint Hessians
+then come from their callbacks, from finite differences or are absent, exactly as without a
+strategy.  As soon as a nonlinear constraint carries a strategy, ONE memory per solve
+approximates the SUM of all Lagrangian-Hessian terms declared with a strategy (Nocedal & Wright
+section 18.3; ``LagrangianQN``): its pair is ``s = x+ - x``, ``y = grad_x L_Q(x+, v+) -
+grad_x L_Q(x, v+)`` with ``L_Q`` the part of the Lagrangian whose terms carry a strategy -- the
+objective's ``g+ - g`` when it participates, ``(J(x+) - J(x))' v+`` per participating constraint
+(``ipx_csr_tdiff_dot``: one launch each, the gradients fused into the first).  All
+participating terms must carry equal strategies.  The CG loops see one low-rank term, as for
+the objective alone.  The Lagrangian's Hessian is usually indefinite, so ``LSR1`` is the rule
+to prefer with constraints; ``LBFGS`` skips every pair with ``s'y <= min_curvature ||s|| ||y||``
+as it does for the objective.
 """
 import numbers
 
@@ -49,6 +60,23 @@ class _Strategy:
             type(self).__name__, self.memory, self.init_scale, self._threshold_name,
             self.threshold)
 
+    def _key(self):
+        return (type(self), self.memory, self.init_scale, self.threshold)
+
+    def __eq__(self, other):
+        """Equal strategies: the same class, ``memory``, ``init_scale`` and threshold (what the
+        terms of one Lagrangian memory must agree on)."""
+        if not isinstance(other, _Strategy):
+            return NotImplemented
+        return self._key() == other._key()
+
+    def __ne__(self, other):
+        eq = self.__eq__(other)
+        return eq if eq is NotImplemented else not eq
+
+    def __hash__(self):
+        return hash(self._key())
+
 
 class LBFGS(_Strategy):
     """Limited-memory BFGS approximation of the objective's Hessian.
@@ -70,11 +98,16 @@ class LBFGS(_Strategy):
     pivoting; a pivot at or below ``1e-14 max|entry|`` skips the pair too (a guard: with every
     ``s'y > 0`` the matrix is invertible).
 
-    Limitation: only the objective is approximated, and a pair is only stored along steps of
-    positive curvature.  On an objective with negative curvature along the steps the solver
-    takes (the Coulomb energy of ``Elec`` in the test problems) every pair after the first few is
-    skipped, ``B`` stops changing and the solve can run out of iterations; ``LSR1`` stores
-    such pairs.
+    Limitation: a pair is only stored along steps of positive curvature.  On an objective with
+    negative curvature along the steps the solver takes (the Coulomb energy of ``Elec`` in the
+    test problems) every pair after the first few is skipped, ``B`` stops changing and the solve
+    can run out of iterations; ``LSR1`` stores such pairs.
+
+    On a constraint (``NonlinearConstraint(..., hess=LBFGS())``) the memory approximates the
+    Hessian of the Lagrangian's participating terms (module header), ``y`` is the difference of
+    their gradients with the new multipliers, and the same skip rule applies: pairs with
+    ``s'y <= min_curvature ||s|| ||y||`` are skipped.  The Lagrangian's Hessian is usually
+    indefinite, so prefer ``LSR1`` with constraints.
 
     Parameters
     ----------
@@ -116,6 +149,10 @@ class LSR1(_Strategy):
     oldest pair is dropped.  ``s'Bs`` and ``||y - Bs||`` follow from the Gram of ``[S Y]`` and
     ``C`` (no extra pass over the vectors).
 
+    On a constraint (``NonlinearConstraint(..., hess=LSR1())``) the memory approximates the
+    Hessian of the Lagrangian's participating terms (module header).  That Hessian is usually
+    indefinite, which this rule represents: it is the one to prefer with constraints.
+
     Parameters
     ----------
     memory : int, 1 <= memory <= 32
@@ -141,7 +178,7 @@ def is_strategy(hess):
 
 
 class LowRankTerm:
-    """The objective's term ``B`` of the Lagrangian Hessian: an x-space device operator
+    """The memory's term ``B`` of the Lagrangian Hessian: an x-space device operator
     (``backend_hip.hessian_operator`` pads it in z-space).  A view of the memory: valid until
     the memory's next update, which is the next Hessian the solver asks for."""
     device_operator = True
@@ -265,3 +302,186 @@ def device_hessian(strategy, memo, n):
         g = memo.lookup(xt)
         return memory.observe(dm.as_dvec(xt), dm.as_dvec(g))
     return hess, memory
+
+
+# ---- one memory for every Lagrangian term declared with a strategy -----------------------------
+class QNRequest:
+    """What the Hessian callback of a participating term returns: the memoised gradient at the
+    point (the objective: ``g``) or the constraint's Jacobian there and its multipliers (``J``,
+    ``v``: what a callable ``hess(x, v)`` would have got).  The Lagrangian's requests are
+    resolved together into the memory's one term (``LagrangianQN.resolve``)."""
+
+    def __init__(self, n, g=None, J=None, v=None):
+        self.g, self.J, self.v = g, J, v
+        self.shape = (int(n), int(n))
+
+    def dot(self, p):
+        from . import _hip
+        raise _hip.IpxError("a quasi-Newton Hessian term is part of the Lagrangian's one memory "
+                            "(LagrangianQN); it has no product of its own")
+
+
+def participating(hess, constraints):
+    """The strategies of a call, the objective's first -- or [] when no constraint carries one
+    (then a strategy objective keeps its own memory).  Unequal strategies are a ValueError."""
+    cons = [c._hess for c in constraints if is_strategy(getattr(c, "_hess", None))]
+    if not cons:
+        return []
+    found = ([hess] if is_strategy(hess) else []) + cons
+    for other in found[1:]:
+        if other != found[0]:
+            raise ValueError(
+                "quasi-Newton Hessians of one problem share ONE memory (the Lagrangian's), so "
+                "they must be equal strategies -- the same class, memory, init_scale and "
+                "threshold: got %r and %r; pass equal ones, or give one of the terms a Hessian "
+                "callback or finite differences" % (found[0], other))
+    return found
+
+
+def tdiff_dot(pattern, val_new, val_old, v, y, base=None, accumulate=False):
+    """``y (+)= [base[0] - base[1]] + (J_new - J_old)' v`` for two value arrays on ``pattern``
+    (``device.CSRPattern`` of J), all device tensors: one launch on the transposed pattern."""
+    from . import _hip
+    from .device import _p, stream_ptr
+    tpat, perm = pattern.transpose()
+    m, n = pattern.shape
+    _hip.call("ipx_csr_tdiff_dot", n, m, pattern.nnz, _p(tpat.indptr), _p(tpat.indices), _p(perm),
+              _p(tpat.tiles), tpat.ntiles, _p(val_new), _p(val_old), _p(v),
+              _p(base[0]) if base is not None else None,
+              _p(base[1]) if base is not None else None, _p(y), 1 if accumulate else 0,
+              stream_ptr())
+    return y
+
+
+class LagrangianQN:
+    """The one memory of a solve whose constraints carry a strategy.  ``resolve`` replaces the
+    ``QNRequest``s among the Lagrangian's Hessian terms by the memory's ``LowRankTerm``, put
+    first (``backend_hip.hessian_operator`` takes it as ``lowrank``); at every point but the
+    first it forms ``y`` from the requests and the values kept from the previous point and
+    calls ``ipx_lowrank_update`` with ``s = x - x_prev``.  The same ``x`` again (new multipliers
+    across barrier levels) gives ``s = 0``, which the update kernel ignores and does not count.
+
+    A sparse Jacobian on the pattern object of the previous point goes through
+    ``ipx_csr_tdiff_dot``; a dense one, or a pattern that changed, through two transposed
+    products (correct, unfused).  ``host_callbacks``: points, gradients, Jacobians and
+    multipliers arrive as numpy / scipy objects and are uploaded here (a sparse Jacobian onto
+    the previous point's pattern object when its structure is the same)."""
+
+    def __init__(self, strategy, n, host_callbacks=False):
+        self.strategy, self.n = strategy, int(n)
+        self.host_callbacks = bool(host_callbacks)
+        self.memory = None
+        self.x_prev = self.g_prev = self.J_prev = None
+        self._x_host = None
+        self.fused_launches = self.fallback_terms = 0
+
+    # ---- what the requests hold, on the device
+    def _point(self, x):
+        from .device import DVec
+        if self.host_callbacks:
+            return DVec.from_host(x)
+        return x if isinstance(x, DVec) else DVec(x)
+
+    def _gradient(self, g):
+        import torch
+        from .device import DVec
+        if self.host_callbacks:
+            return DVec.from_host(g)
+        return g if isinstance(g, DVec) else DVec(g.to(torch.float64).reshape(-1))
+
+    def _jacobian(self, J, prev):
+        """-> DeviceCSR | DeviceDense"""
+        import scipy.sparse as sps
+        from .device import DeviceCSR
+        from .dense import DeviceDense
+        if not self.host_callbacks:
+            return J
+        if sps.issparse(J):
+            return DeviceCSR.from_scipy(J, pattern=prev.pattern if isinstance(prev, DeviceCSR)
+                                        else None)
+        return DeviceDense.from_host(J)
+
+    def _multipliers(self, v, m):
+        from .device import DVec
+        v = DVec.from_host(v) if self.host_callbacks else (v if isinstance(v, DVec) else DVec(v))
+        if len(v) != m:
+            from . import _hip
+            raise _hip.IpxError("quasi-Newton constraint Hessian: %d multipliers for a Jacobian "
+                                "of %d rows" % (len(v), m))
+        return v
+
+    # ---- the update
+    def _y(self, g, jacs, vs):
+        from .device import DVec, DeviceCSR, _empty
+        y = None
+        base = (g.t, self.g_prev.t) if g is not None else None
+        for J, J_old, v in zip(jacs, self.J_prev, vs):
+            if isinstance(J, DeviceCSR) and isinstance(J_old, DeviceCSR) \
+                    and J.pattern is J_old.pattern:
+                first = y is None
+                if first:
+                    y = DVec(_empty(self.n))
+                tdiff_dot(J.pattern, J.val, J_old.val, v.t, y.t, base=base if first else None,
+                          accumulate=not first)
+                if first:
+                    base = None
+                self.fused_launches += 1
+                continue
+            if y is None and base is not None:
+                y, base = g - self.g_prev, None
+            c = J.T.dot(v) - J_old.T.dot(v)
+            y = c if y is None else y + c
+            self.fallback_terms += 1
+        if y is None:
+            y = g - self.g_prev
+        return y
+
+    def observe(self, x, requests):
+        from . import _hip
+        from .device import _p, stream_ptr
+        if self.host_callbacks:
+            if self._x_host is not None and np.array_equal(x, self._x_host):
+                return self.memory.term             # the same point again: not an update
+            self._x_host = np.array(x, dtype=float, copy=True)
+        if self.memory is None:
+            self.memory = _Memory(self.strategy, self.n)
+        xd = self._point(x)
+        if len(xd) != self.n:
+            raise _hip.IpxError("quasi-Newton Hessian: a point of %d entries, the memory has %d"
+                                % (len(xd), self.n))
+        gs = [r for r in requests if r.g is not None]
+        cons = [r for r in requests if r.J is not None]
+        if len(gs) > 1 or (self.J_prev is not None and len(cons) != len(self.J_prev)):
+            raise _hip.IpxError("quasi-Newton Hessian: the participating terms changed during a "
+                                "solve")
+        g = self._gradient(gs[0].g) if gs else None
+        prev = self.J_prev if self.J_prev is not None else [None] * len(cons)
+        jacs = [self._jacobian(r.J, p) for r, p in zip(cons, prev)]
+        if self.x_prev is not None:
+            vs = [self._multipliers(r.v, J.shape[0]) for r, J in zip(cons, jacs)]
+            s = xd - self.x_prev
+            y = self._y(g, jacs, vs)
+            st = self.strategy
+            _hip.call("ipx_lowrank_update", st.kind, self.n, st.memory, st.init_value,
+                      st.threshold, _p(self.memory.W), _p(s.t), _p(y.t), _p(self.memory.state),
+                      _p(self.memory.part), stream_ptr())
+        # what the next pair needs of this point.  Host callbacks: everything was uploaded into
+        # arrays of its own.  Device callbacks: the Jacobians are the memo's private copies
+        # (fd_hessian.DeviceMemo: nnz doubles, or the dense buffer); the point and the gradient
+        # may be buffers their owners write again
+        copy = (lambda t: t) if self.host_callbacks else (lambda t: t.copy())
+        self.x_prev = copy(xd)
+        self.g_prev = copy(g) if g is not None else None
+        self.J_prev = jacs
+        return self.memory.term
+
+    def resolve(self, terms, x):
+        """A list of Hessian terms with its ``QNRequest``s replaced by the memory's term, put
+        first; the other terms keep their order."""
+        requests = [t for t in terms if isinstance(t, QNRequest)]
+        if not requests:
+            return list(terms)
+        return [self.observe(x, requests)] + [t for t in terms if not isinstance(t, QNRequest)]
+
+    def counts(self):
+        return self.memory.counts() if self.memory is not None else (0, 0)
