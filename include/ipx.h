@@ -857,6 +857,41 @@ void ipx_fd_assemble_sym_host(int64_t n, const int32_t *rowptr, const int32_t *c
                               const double *dx, const unsigned char *one_sided,
                               const int32_t *slot, int32_t accumulate, double *val);
 
+/* ---- block-tridiagonal direct solve with S = A A' (csrc/blocktri.hip): block cyclic reduction
+ * for half bandwidths past ipx_banded_kmax() up to ipx_blocktri_kmax() = 64.  S (rows in the
+ * order `perm`, NULL = identity) is taken as block tridiagonal in blocks of b = 16, 32 or 64
+ * (b >= half bandwidth k), N = ceil(m / b) block rows, the padded tail rows with a unit
+ * diagonal.  The caller owns all storage: `ws` holds ipx_blocktri_ws_doubles(m, b) doubles,
+ * [D | E | V | diag0 | r | y]: N b^2 doubles each for D, E, V (row-major b x b blocks; after the
+ * factorization the Cholesky factor's blocks), N b each for the rest (the solve's work vectors
+ * among them: solves on one `ws` are ordered by the stream).  Nothing is allocated and no handle
+ * is kept.  Fixed-order fp64: the same values give the same bits. */
+int ipx_blocktri_kmax(void);
+int64_t ipx_blocktri_ws_doubles(int64_t m, int32_t b);
+/* out[0] = levels of the reduction (1 + ceil(log2 N): the last block counts as one), out[1] =
+ * the number of surviving block rows at which one workgroup takes all remaining levels in a
+ * single launch; returns how many levels run as launches of their own before that (>= 0), or
+ * IPX_EINVAL.  Launches: factor 2 + 2 x that, solve 2 + 2 x that. */
+int ipx_blocktri_levels(int64_t m, int32_t b, int32_t out[2]);
+/* D[I] = S[I, I], E[I] = S[I, I - 1] (E[0] = 0), N blocks each and nothing past them; entries
+ * further than k from the diagonal are written as zeros without being formed.  CSR rows sorted,
+ * every (row, column) once, as for ipx_aat_band_w: repeated entries are summed by the caller
+ * before this (DeviceCSR.from_scipy does), the join does not sum them.  A merge join per entry,
+ * products added in column order. */
+int ipx_aat_blocktri(int64_t m, int32_t b, int32_t k, const int32_t *rowptr,
+                     const int32_t *colidx, const double *val, const int32_t *perm, double *D,
+                     double *E, void *stream);
+/* Factor the blocks D, E (left as they are -- unless D == ws and E == ws + N b^2: in place, no
+ * copy).  flag[0] (cleared first): bit 0 -- a pivot fell below 2^-43 of its original diagonal
+ * entry (numerically rank deficient; the factorization is complete); bit 2 (with bit 0) -- a
+ * pivot was <= 0 (not positive definite; the factors are not usable). */
+int ipx_blocktri_factor(int64_t m, int32_t b, const double *D, const double *E, double *ws,
+                        int *flag, void *stream);
+/* x = S^-1 w (m entries, in the order of `perm`; w and x may not alias; nothing past x[m - 1]
+ * is written): triangular solves with the factor's blocks, backward stable. */
+int ipx_blocktri_solve(int64_t m, int32_t b, double *ws, const double *w, double *x,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

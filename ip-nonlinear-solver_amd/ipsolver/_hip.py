@@ -134,6 +134,11 @@ _SIGNATURES = {
     "ipx_fd_perturb": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble": [_I64, _I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P,
                         _P, _P],
+    "ipx_blocktri_kmax": [],
+    "ipx_blocktri_levels": [_I64, _I32, _P],
+    "ipx_aat_blocktri": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "ipx_blocktri_factor": [_I64, _I32, _P, _P, _P, _P, _P],
+    "ipx_blocktri_solve": [_I64, _I32, _P, _P, _P, _P],
     "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                             _I32, _P, _P],
 }
@@ -149,8 +154,9 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_lowrank_state_doubles": _I64, "ipx_lowrank_part_doubles": _I64,
              "ipx_lowrank_middle_host": None, "ipx_fd_steps_host": None,
              "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None,
-             "ipx_fd_assemble_sym_host": None}
-_EXTRA_ARGTYPES = {"ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
+             "ipx_fd_assemble_sym_host": None, "ipx_blocktri_ws_doubles": _I64}
+_EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
+                   "ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
                    "ipx_dense_padded": [_I64], "ipx_gram_ws_doubles": [_I64, _I32],
                    "ipx_peer_create": [_I32, _I32, _I64],
                    "ipx_peer_destroy": [_P], "ipx_peer_halo_capacity": [_P],

@@ -175,8 +175,12 @@ class BoxSchurNormalSolver:
             B = dv.DeviceCSR(self.A_R.pattern, self.A_R.val * sw[idx])
             self.B = B
             mR = B.shape[0]
-            self.inner = DenseNormalSolver(B) if mR <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE \
-                else IterativeNormalSolver(B)
+            # (the wide-band policy, projector.wide_band: block cyclic reduction when asked for)
+            from .projector import wide_band_inner
+            self.inner = wide_band_inner(B)
+            if self.inner is None:
+                self.inner = DenseNormalSolver(B) \
+                    if mR <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE else IterativeNormalSolver(B)
         else:
             self.inner = BandedNormalSolver(self.A_R, col_weights=self.wcol)   # Sigma = A_R W A_R'
         bits = int(flag.item())

@@ -425,6 +425,28 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     partitioned over the ranks (ipsolver/sharded.py), the result carries global arrays.
     """
     options = dict(options)
+    # ADDITIVE option: which solver takes a sparse Jacobian whose A A' is banded past the banded
+    # kernels' half bandwidth ("iterative", the default, or "block-tridiagonal":
+    # projector.wide_band).  Held for the duration of the call -- every factorization of the
+    # run is made under it, not the first one only.
+    from . import projector
+    policy = projector.check_wide_band(options.pop("wide_band", projector.wide_band_policy()))
+    projector._last_solver[0] = None
+    with projector.wide_band(policy):
+        result = _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol,
+                                       sparse_jacobian, options, callback, max_iter, verbose)
+    # the solver behind the projections the run was handed last, made then or reused from a
+    # cache ("BoxSchurNormalSolver/<inner>" for the box-Schur elimination, "SVDProjector" after
+    # the SVD exit; None when this process's projector factored nothing: no constraint rows, or
+    # a row-sharded backend that builds its solvers itself).
+    # An attribute, not a key: ``result.keys()`` stays the reference's set of fields.
+    object.__setattr__(result, "normal_solver", projector.last_normal_solver())
+    return result
+
+
+def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, sparse_jacobian,
+                          options, callback, max_iter, verbose):
+    options = dict(options)
     shard = _shard_request(options)
     if _qn.is_strategy(hess) and options.get("constant_hessian", False):
         raise ValueError("options={'constant_hessian': True} cannot be combined with a "

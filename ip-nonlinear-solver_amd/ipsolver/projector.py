@@ -22,6 +22,7 @@ matvecs (``SVDProjector``).
 """
 from warnings import warn
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -32,6 +33,59 @@ from . import device as dv
 from .device import DVec, DeviceCSR, _p, stream_ptr, ctx
 
 _F64 = torch.float64
+
+# ---- what takes a sparse A whose A A' is banded past the banded kernels' half bandwidth --------
+# "iterative" (default): the dense Cholesky while it fits, else the preconditioned CG;
+# "block-tridiagonal": block cyclic reduction (blocktri.py) up to half bandwidth 64.  Scoped:
+# ``with wide_band("block-tridiagonal"): ...``; part of the key of every cached factorization.
+WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal")
+_wide_band = ["iterative"]
+_last_solver = [None]
+
+
+def check_wide_band(policy):
+    if policy not in WIDE_BAND_POLICIES:
+        raise ValueError("wide_band must be one of %s, not %r"
+                         % (", ".join(repr(p) for p in WIDE_BAND_POLICIES), policy))
+    return policy
+
+
+def wide_band_policy():
+    return _wide_band[0]
+
+
+@contextlib.contextmanager
+def wide_band(policy):
+    """Hold the wide-band policy for the duration of the block (restored on any exit)."""
+    previous, _wide_band[0] = _wide_band[0], check_wide_band(policy)
+    try:
+        yield
+    finally:
+        _wide_band[0] = previous
+
+
+def solver_name(solver):
+    """Class name of a normal-equation solver; ``Outer/Inner`` for the box-Schur elimination."""
+    if solver is None:
+        return None
+    name = type(solver).__name__
+    inner = getattr(solver, "inner", None)
+    return name if inner is None else "%s/%s" % (name, type(inner).__name__)
+
+
+def last_normal_solver():
+    """``solver_name`` of the factorization ``projections`` handed out last, made then or taken
+    from its cache ("SVDProjector" for the SVD exit); None: none yet, or a Jacobian without
+    rows, which has nothing to factor."""
+    return _last_solver[0]
+
+
+def note_solver(ops):
+    P = getattr(ops[0], "projector", None)
+    if isinstance(P, NormalEquationProjector):
+        _last_solver[0] = solver_name(P.solver)
+    else:
+        _last_solver[0] = None if P is None else type(P).__name__
 
 
 def half_bandwidth_of_aat(pattern):
@@ -468,16 +522,24 @@ def _box_schur_applies(A, kmax, any_sparsity=False):
     ``any_sparsity``, of any pattern (the Schur complement then goes to the dense or the
     iterative solver: boxschur.BoxSchurNormalSolver)."""
     from .boxschur import analysis_for
-    from .device_mode import RowSelection
     an = analysis_for(A.pattern)
     if not an.worthwhile:
         return False
     if any_sparsity:
         return len(an.general) > 0
+    return _general_rows_half_bandwidth(A) <= kmax
+
+
+def _general_rows(A):
+    """The selection of the rows the box-Schur elimination leaves to its inner solver (made
+    once per pattern, cached on it; boxschur.py reads the same attribute)."""
+    from .boxschur import analysis_for
+    from .device_mode import RowSelection
     cache = getattr(A.pattern, "_ipx_box_general_pattern", None)
     if cache is None:
+        an = analysis_for(A.pattern)
         cache = A.pattern._ipx_box_general_pattern = RowSelection(A.pattern, an.general, None)
-    return _symbolic_for(cache.pattern).k <= kmax
+    return cache
 
 
 class PcgArgs(ctypes.Structure):
@@ -642,13 +704,43 @@ def as_device_matrix(A):
     return DeviceDense.from_host(np.asarray(A, dtype=float))
 
 
+def _general_rows_half_bandwidth(A):
+    """Half bandwidth (after reordering) of ``A_R A_R'``, A_R the rows the box-Schur elimination
+    leaves to its inner solver."""
+    return _symbolic_for(_general_rows(A).pattern).k
+
+
+def wide_band_inner(B):
+    """The box-Schur elimination's inner solver for ``B B'`` of any sparsity under the policy
+    in force: the block-tridiagonal solver when the policy asks for it and the half bandwidth
+    allows it, else None (the caller's dense / iterative choice)."""
+    if wide_band_policy() != "block-tridiagonal":
+        return None
+    from .blocktri import BlockTridiagonalNormalSolver
+    if _symbolic_for(B.pattern).k > _hip.load().ipx_blocktri_kmax():
+        return None
+    return BlockTridiagonalNormalSolver(B)
+
+
 def normal_solver_for(A, deferred=None):
     """The ``(A A')^-1`` solver ``projections`` picks for a full-row-rank device matrix."""
+    solver = _pick_normal_solver(A, deferred)
+    _last_solver[0] = solver_name(solver)
+    return solver
+
+
+def _pick_normal_solver(A, deferred=None):
     from .dense import DenseNormalSolver, DeviceDense
     if isinstance(A, DeviceDense):
         return DenseNormalSolver(A)
     kmax = _hip.load().ipx_banded_kmax()
     m = A.shape[0]
+    # the wide-band policy (see ``wide_band``): dense A and half bandwidths <= kmax keep their
+    # order; three places differ, marked (W1)-(W3)
+    wide = wide_band_policy() == "block-tridiagonal"
+    if wide:
+        from .blocktri import BlockTridiagonalNormalSolver
+        bt_kmax = _hip.load().ipx_blocktri_kmax()
     if half_bandwidth_of_aat(A.pattern) > kmax and _box_schur_applies(A, kmax):
         # the barrier problem's augmented Jacobian: a general row couples with the two bound
         # rows of each of its variables, no reordering of A A' is narrow -- skip the attempt
@@ -656,7 +748,14 @@ def normal_solver_for(A, deferred=None):
         try:
             return BoxSchurNormalSolver(A)
         except BandedNotDecoupled:
-            pass
+            if wide:                            # (W1) the Schur complement is such a band
+                return BoxSchurNormalSolver(A, any_sparsity=True)
+    if wide and _box_schur_applies(A, kmax, any_sparsity=True) \
+            and kmax < _general_rows_half_bandwidth(A) <= bt_kmax:
+        # (W2) bound rows eliminated in closed form, the general rows' Schur complement
+        # J (I - W) J' + S^2 (the pattern of A_R A_R') factored directly, for any m
+        from .boxschur import BoxSchurNormalSolver
+        return BoxSchurNormalSolver(A, any_sparsity=True)
     k = _symbolic_for(A.pattern).k
     if k <= kmax:
         try:
@@ -667,6 +766,8 @@ def normal_solver_for(A, deferred=None):
             # decouple).  When they do not, a serial sweep would take 80-100 ms per solve at
             # m = 1e5: the device-resident preconditioned CG is 20x faster and as accurate
             # after the projector's refinement (profiles/r02_banded_by_bandwidth.txt).
+            if wide:
+                return BlockTridiagonalNormalSolver(A)      # (W1) blocks of 16, any m
             if m > DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
                 return IterativeNormalSolver(A)
     if _box_schur_applies(A, kmax):
@@ -676,7 +777,10 @@ def normal_solver_for(A, deferred=None):
         except BandedNotDecoupled:
             # the Schur complement of the general rows is such a coupled wide band: the
             # elimination buys nothing, solve with A itself by the paths below
-            pass
+            if wide:
+                return BoxSchurNormalSolver(A, any_sparsity=True)          # (W1)
+    if wide and kmax < k <= bt_kmax:
+        return BlockTridiagonalNormalSolver(A)  # (W3) block cyclic reduction, any m
     if m <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
         return DenseNormalSolver(A)             # wide band: dense Cholesky of A A'
     if _box_schur_applies(A, kmax, any_sparsity=True):
@@ -735,13 +839,15 @@ def projections(A, method=None, orth_tol=1e-12, max_refin=3, tol=1e-15, deferred
     # reference to the tensor it was made for: a reassigned ``A.val`` can then never collide
     # with a collected tensor's id.
     t, version = _values_version(A)
-    key = (method, orth_tol, max_refin, tol, version)
+    key = (method, orth_tol, max_refin, tol, version, wide_band_policy())
     cached = getattr(A, "_ipx_projections", None)
     if cached is not None and version is not None and cached[0] == key and cached[2] is t:
         # (a caller that cannot take a pending verdict along gets it settled first)
         if deferred is not None or confirm(A, cached[1]):
+            note_solver(cached[1])           # (a factorization reused is still the last one)
             return cached[1]
     out = _projections(A, method, orth_tol, max_refin, tol, deferred)
+    note_solver(out)
     try:
         A._ipx_projections = (key, out, t)
     except AttributeError:
@@ -822,3 +928,6 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
         return SVDProjector(A_caller, orth_tol, max_refin, tol).operators()
     return NormalEquationProjector(A, solver, orth_tol, max_refin, row_perm=row_perm,
                                    lazy_norm=deferred is not None).operators()
+
+
+from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: E402,F401  (public here)

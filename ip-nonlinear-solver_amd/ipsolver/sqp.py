@@ -181,6 +181,7 @@ class ChainStages:
         memo = getattr(pt.A, "_ipx_settled", None)
         if memo_key is not None and memo is not None and _same_key(memo[0], memo_key):
             pt.Z, pt.LS, pt.Y, pt.v, pt.opt, pt.viol, pt.norm_b = memo[1]
+            projector.note_solver((pt.Z,))
             sc.STATS["settles_reused"] += 1
             return
         ops = projector.projections(pt.A, method, deferred=chain)
@@ -417,7 +418,8 @@ def _settle_key(pt, method):
     tens = (getattr(pt.A, "val", None), getattr(pt.c, "t", None), getattr(pt.b, "t", None))
     if any(t is None or not hasattr(t, "_version") for t in tens):
         return None
-    return (method,) + tuple((t, t._version) for t in tens)
+    from .projector import wide_band_policy          # (a factorization belongs to its policy)
+    return ((method, wide_band_policy()),) + tuple((t, t._version) for t in tens)
 
 
 def _same_key(a, b):
