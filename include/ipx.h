@@ -892,6 +892,39 @@ int ipx_blocktri_factor(int64_t m, int32_t b, const double *D, const double *E, 
 int ipx_blocktri_solve(int64_t m, int32_t b, double *ws, const double *w, double *x,
                        void *stream);
 
+/* ---- bordered direct solve with S = A A' (csrc/bordered.hip): A = [B | C], C the p dense columns
+ * (1 <= p <= ipx_border_pmax() = 32), S = S_B + C C' by the Woodbury identity on top of a direct
+ * solve with S_B = B B':  S^-1 w = u - Y z,  u = S_B^-1 w,  Y = S_B^-1 C,  K = I + C' Y,
+ * K z = Y' w.  C and Y are column-major m x p, K and its Cholesky factor L row-major p x p.  The
+ * caller owns all storage and runs the inner solves; nothing is allocated, no handle is kept.
+ * Rows are dealt to workgroups in chunks of ipx_border_rows_per_group(); the partial sums of a
+ * launch are ipx_border_groups(m) blocks, always added in ascending order (no atomics): the same
+ * values give the same bits. */
+int ipx_border_pmax(void);
+int ipx_border_rows_per_group(void);
+/* number of partial blocks of ipx_border_gram (p * p doubles each) and ipx_border_tdot (p each):
+ * min(ceil(m / rows_per_group), 512); IPX_EINVAL for m < 1 */
+int ipx_border_groups(int64_t m);
+/* C = 0, then C[dst[i]] = val[src[i]] for i < nnz (dst = row + m * border column; every
+ * (row, column) once, dst[i] < m * p: the caller's index lists, made once per pattern) */
+int ipx_border_scatter(int64_t m, int32_t p, int64_t nnz, const double *val, const int32_t *src,
+                       const int64_t *dst, double *C, void *stream);
+/* part[g] = the p x p block of C' Y over the rows of group g */
+int ipx_border_gram(int64_t m, int32_t p, const double *C, const double *Y, double *part,
+                    void *stream);
+/* K = I + sum_g part[g] (all p * p entries written; the lower triangle is what is factored),
+ * L = its Cholesky factor (zeros above the diagonal), by one workgroup in LDS.  info[0]: bit 0 --
+ * a pivot fell below 2^-43 of its diagonal entry; bit 2 (with bit 0) -- a pivot was <= 0;
+ * info[1] = trace(K).  `m` selects the number of partial blocks only. */
+int ipx_border_chol(int64_t m, int32_t p, const double *part, double *K, double *L, double *info,
+                    void *stream);
+/* part[g] = the p partial sums of t = Y' w over the rows of group g */
+int ipx_border_tdot(int64_t m, int32_t p, const double *Y, const double *w, double *part,
+                    void *stream);
+/* z = (L L')^-1 (sum_g part[g]), v[r] = u[r] - sum_j Y[r, j] z[j]; v may be u */
+int ipx_border_apply(int64_t m, int32_t p, const double *Y, const double *L, const double *part,
+                     const double *u, double *v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,14 @@ _SIGNATURES = {
     "ipx_aat_blocktri": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "ipx_blocktri_factor": [_I64, _I32, _P, _P, _P, _P, _P],
     "ipx_blocktri_solve": [_I64, _I32, _P, _P, _P, _P],
+    "ipx_border_pmax": [],
+    "ipx_border_rows_per_group": [],
+    "ipx_border_groups": [_I64],
+    "ipx_border_scatter": [_I64, _I32, _I64, _P, _P, _P, _P, _P],
+    "ipx_border_gram": [_I64, _I32, _P, _P, _P, _P],
+    "ipx_border_chol": [_I64, _I32, _P, _P, _P, _P, _P],
+    "ipx_border_tdot": [_I64, _I32, _P, _P, _P, _P],
+    "ipx_border_apply": [_I64, _I32, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                             _I32, _P, _P],
 }

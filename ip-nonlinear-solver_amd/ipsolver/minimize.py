@@ -431,8 +431,13 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     # run is made under it, not the first one only.
     from . import projector
     policy = projector.check_wide_band(options.pop("wide_band", projector.wide_band_policy()))
+    # ADDITIVE option: up to this many dense columns of a sparse Jacobian (global parameters of a
+    # staged problem) are split off as a border of a banded / block-tridiagonal A A'
+    # (projector.border_columns, bordered.py); 0, the default: off.  Held like the policy.
+    border = projector.check_border_columns(
+        options.pop("border_columns", projector.border_columns_limit()))
     projector._last_solver[0] = None
-    with projector.wide_band(policy):
+    with projector.wide_band(policy), projector.border_columns(border):
         result = _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol,
                                        sparse_jacobian, options, callback, max_iter, verbose)
     # the solver behind the projections the run was handed last, made then or reused from a

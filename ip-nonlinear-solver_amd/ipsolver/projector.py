@@ -64,13 +64,71 @@ def wide_band(policy):
         _wide_band[0] = previous
 
 
+# ---- dense columns on top of a band (bordered.py) -------------------------------------------
+# Up to this many columns of a sparse A may be split off as a border when the rest is banded /
+# block tridiagonal in A A' (0, the default: off, every path as without the option).  Scoped like
+# the wide-band policy -- ``with border_columns(4): ...`` -- and part of the same cache keys.
+_border = [0]
+
+
+def check_border_columns(limit):
+    pmax = _hip.load().ipx_border_pmax()
+    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) \
+            or not 0 <= limit <= pmax:
+        raise ValueError("border_columns must be an integer in 0 ... %d, not %r" % (pmax, limit))
+    return int(limit)
+
+
+def border_columns_limit():
+    return _border[0]
+
+
+@contextlib.contextmanager
+def border_columns(limit):
+    """Hold the border-column limit for the duration of the block (restored on any exit)."""
+    previous, _border[0] = _border[0], check_border_columns(limit)
+    try:
+        yield
+    finally:
+        _border[0] = previous
+
+
+def border_reach():
+    """The half bandwidth the band of a bordered matrix may have under the policy in force."""
+    lib = _hip.load()
+    return lib.ipx_blocktri_kmax() if wide_band_policy() == "block-tridiagonal" \
+        else lib.ipx_banded_kmax()
+
+
+def _border_split_for(pattern):
+    from .bordered import border_split
+    limit = border_columns_limit()
+    if limit < 1:
+        return None
+    return border_split(pattern, border_reach(), limit)
+
+
+def bordered_solver(A):
+    """``BorderedNormalSolver`` for a sparse A when the option is on, the split applies and the
+    solver does not refuse; else None (the caller's other choices)."""
+    split = _border_split_for(A.pattern) if isinstance(A, DeviceCSR) else None
+    if split is None:
+        return None
+    from .bordered import BorderedNormalSolver, BorderedRefused
+    try:
+        return BorderedNormalSolver(A, split)
+    except BorderedRefused:
+        return None
+
+
 def solver_name(solver):
-    """Class name of a normal-equation solver; ``Outer/Inner`` for the box-Schur elimination."""
+    """Class name of a normal-equation solver; ``Outer/Inner`` (recursively) for a solver that
+    sits on an inner one: the box-Schur elimination, the bordered solver."""
     if solver is None:
         return None
     name = type(solver).__name__
     inner = getattr(solver, "inner", None)
-    return name if inner is None else "%s/%s" % (name, type(inner).__name__)
+    return name if inner is None else "%s/%s" % (name, solver_name(inner))
 
 
 def last_normal_solver():
@@ -713,7 +771,11 @@ def _general_rows_half_bandwidth(A):
 def wide_band_inner(B):
     """The box-Schur elimination's inner solver for ``B B'`` of any sparsity under the policy
     in force: the block-tridiagonal solver when the policy asks for it and the half bandwidth
-    allows it, else None (the caller's dense / iterative choice)."""
+    allows it, else None (the caller's dense / iterative choice).  With border columns allowed
+    (``border_columns``) the bordered solver comes first."""
+    solver = bordered_solver(B)
+    if solver is not None:
+        return solver
     if wide_band_policy() != "block-tridiagonal":
         return None
     from .blocktri import BlockTridiagonalNormalSolver
@@ -735,6 +797,20 @@ def _pick_normal_solver(A, deferred=None):
         return DenseNormalSolver(A)
     kmax = _hip.load().ipx_banded_kmax()
     m = A.shape[0]
+    if border_columns_limit() > 0:
+        # a band plus a few dense columns (bordered.py), before everything else; a refusal in
+        # either place goes on with the order below
+        solver = bordered_solver(A)                                        # (D1)
+        if solver is not None:
+            return solver
+        if _box_schur_applies(A, kmax, any_sparsity=True) \
+                and _border_split_for(_general_rows(A).pattern) is not None:
+            # (D2) bound rows eliminated in closed form; the general rows are such a matrix
+            from .bordered import BorderedNormalSolver
+            from .boxschur import BoxSchurNormalSolver
+            solver = BoxSchurNormalSolver(A, any_sparsity=True)
+            if isinstance(solver.inner, BorderedNormalSolver):
+                return solver
     # the wide-band policy (see ``wide_band``): dense A and half bandwidths <= kmax keep their
     # order; three places differ, marked (W1)-(W3)
     wide = wide_band_policy() == "block-tridiagonal"
@@ -803,6 +879,8 @@ def _banded_row_order(A):
         return None
     if _box_schur_applies(A, kmax):
         return None
+    if _border_split_for(A.pattern) is not None:
+        return None             # (the bordered solver's band has its own order; A A' is full)
     sym = _symbolic_for(A.pattern)
     return sym.perm if (sym.k <= kmax and sym.perm is not None) else None
 
@@ -839,7 +917,7 @@ def projections(A, method=None, orth_tol=1e-12, max_refin=3, tol=1e-15, deferred
     # reference to the tensor it was made for: a reassigned ``A.val`` can then never collide
     # with a collected tensor's id.
     t, version = _values_version(A)
-    key = (method, orth_tol, max_refin, tol, version, wide_band_policy())
+    key = (method, orth_tol, max_refin, tol, version, wide_band_policy(), border_columns_limit())
     cached = getattr(A, "_ipx_projections", None)
     if cached is not None and version is not None and cached[0] == key and cached[2] is t:
         # (a caller that cannot take a pending verdict along gets it settled first)
@@ -931,3 +1009,4 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
 
 
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: E402,F401  (public here)
+from .bordered import BorderedNormalSolver, BorderedRefused, border_split  # noqa: E402,F401

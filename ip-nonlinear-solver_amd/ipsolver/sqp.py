@@ -418,8 +418,10 @@ def _settle_key(pt, method):
     tens = (getattr(pt.A, "val", None), getattr(pt.c, "t", None), getattr(pt.b, "t", None))
     if any(t is None or not hasattr(t, "_version") for t in tens):
         return None
-    from .projector import wide_band_policy          # (a factorization belongs to its policy)
-    return ((method, wide_band_policy()),) + tuple((t, t._version) for t in tens)
+    # (a factorization belongs to its policy and its border-column limit)
+    from .projector import wide_band_policy, border_columns_limit
+    return ((method, wide_band_policy(), border_columns_limit()),) \
+        + tuple((t, t._version) for t in tens)
 
 
 def _same_key(a, b):
