@@ -925,6 +925,39 @@ int ipx_border_tdot(int64_t m, int32_t p, const double *Y, const double *w, doub
 int ipx_border_apply(int64_t m, int32_t p, const double *Y, const double *L, const double *part,
                      const double *u, double *v, void *stream);
 
+/* ---- linked direct solve with S = A A' (csrc/linked.hip): the rows of A are m_B band rows B and
+ * q link rows D (1 <= q <= ipx_border_pmax(), m = m_B + q, m_B >= 1), in any positions:
+ *     S = [S_B E; E' F],  S_B = B B',  E = B D',  F = D D',  Y = S_B^-1 E,  K = F - E' Y,
+ *     u = S_B^-1 w_B,  K z = w_D - Y' w_B,  v_B = u - Y z,  v_D = z.
+ * The caller owns all storage and runs the inner solves; nothing is allocated, no handle is kept.
+ * Layouts: Dt = D' is n x q ROW-major (entry (c, j) at c * q + j; ipx_border_scatter(n, q, ...)
+ * with dst = column * q + link row fills it), so that the q lanes of a row read q adjacent
+ * doubles per entry of A.  G and Y are column-major m x q with leading dimension m; rows
+ * 0 .. m_B - 1 of G are E, rows m_B .. m - 1 are F; the same rows of Y are S_B^-1 E and ZEROS,
+ * and the gathered w_B carries q zeros at its end: ipx_border_gram(m, q, G, Y, part) and
+ * ipx_border_tdot(m, q, Y, w_B, part) then give the partial blocks of E' Y and Y' w_B in place
+ * (ipx_border_groups(m) of them).  K and L are row-major q x q.  Fixed-order fp64, no atomics: the
+ * same values give the same bits. */
+/* G[dst_row[r] + m j] = sum over the entries e of row r of A (m x n CSR), in storage order, of
+ * val[e] * Dt[colidx[e] * q + j]: one multiply and one add per entry, A read once for all q.
+ * dst_row: band rows to 0 .. m_B - 1, link rows to m_B .. m - 1 (a permutation of 0 .. m - 1;
+ * the product itself takes any permutation and any m >= 1). */
+int ipx_link_spmm(int64_t m, int64_t n, int32_t q, const int32_t *rowptr, const int32_t *colidx,
+                  const double *val, const double *Dt, const int32_t *dst_row, double *G,
+                  void *stream);
+/* K = F - sum_g part[g] (ascending g; all q * q entries written, the lower triangle is what is
+ * factored), L = its Cholesky factor (zeros above the diagonal), by one workgroup in LDS.
+ * info[0]: bit 0 -- a pivot fell below 2^-43 of F_jj, the diagonal entry of S; bit 2 (with
+ * bit 0) -- a pivot was <= 0; info[1] = max_j F_jj / K_jj (infinite for a K_jj <= 0). */
+int ipx_link_chol(int64_t m, int32_t q, const double *G, const double *part, double *K, double *L,
+                  double *info, void *stream);
+/* t = w[d_rows] - sum_g part[g] (the order of ipx_border_apply), z = (L L')^-1 t,
+ * v[b_rows[r]] = u[r] - sum_j Y[r, j] z[j] (r < m_B, j ascending), v[d_rows[j]] = z[j]: v in the
+ * caller's row order, w the caller's right-hand side; v may alias neither w nor u. */
+int ipx_link_apply(int64_t m, int32_t q, const double *Y, const double *L, const double *part,
+                   const double *u, const double *w, const int32_t *b_rows, const int32_t *d_rows,
+                   double *v, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

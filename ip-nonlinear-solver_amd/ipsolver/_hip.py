@@ -147,6 +147,9 @@ _SIGNATURES = {
     "ipx_border_chol": [_I64, _I32, _P, _P, _P, _P, _P],
     "ipx_border_tdot": [_I64, _I32, _P, _P, _P, _P],
     "ipx_border_apply": [_I64, _I32, _P, _P, _P, _P, _P, _P],
+    "ipx_link_spmm": [_I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "ipx_link_chol": [_I64, _I32, _P, _P, _P, _P, _P, _P],
+    "ipx_link_apply": [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                             _I32, _P, _P],
 }

@@ -436,8 +436,13 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     # (projector.border_columns, bordered.py); 0, the default: off.  Held like the policy.
     border = projector.check_border_columns(
         options.pop("border_columns", projector.border_columns_limit()))
+    # ADDITIVE option: up to this many dense rows of a sparse Jacobian (linking constraints of a
+    # staged problem: a budget, a periodicity condition) are split off from a banded /
+    # block-tridiagonal A A' (projector.link_rows, linked.py); 0, the default: off.
+    link = projector.check_link_rows(options.pop("link_rows", projector.link_rows_limit()))
     projector._last_solver[0] = None
-    with projector.wide_band(policy), projector.border_columns(border):
+    with projector.wide_band(policy), projector.border_columns(border), \
+            projector.link_rows(link):
         result = _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol,
                                        sparse_jacobian, options, callback, max_iter, verbose)
     # the solver behind the projections the run was handed last, made then or reused from a

@@ -121,9 +121,62 @@ def bordered_solver(A):
         return None
 
 
+# ---- dense rows on top of a band (linked.py) -------------------------------------------------
+# Up to this many rows of a sparse A may be split off as link rows when the rest is banded / block
+# tridiagonal in A A' (0, the default: off, every path as without the option).  Scoped like the
+# border-column limit -- ``with link_rows(4): ...`` -- and part of the same cache keys.
+_link = [0]
+
+
+def check_link_rows(limit):
+    qmax = _hip.load().ipx_border_pmax()
+    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) \
+            or not 0 <= limit <= qmax:
+        raise ValueError("link_rows must be an integer in 0 ... %d, not %r" % (qmax, limit))
+    return int(limit)
+
+
+def link_rows_limit():
+    return _link[0]
+
+
+@contextlib.contextmanager
+def link_rows(limit):
+    """Hold the link-row limit for the duration of the block (restored on any exit)."""
+    previous, _link[0] = _link[0], check_link_rows(limit)
+    try:
+        yield
+    finally:
+        _link[0] = previous
+
+
+def _link_split_for(pattern):
+    from .linked import link_split
+    limit = link_rows_limit()
+    if limit < 1:
+        return None
+    return link_split(pattern, border_reach(), limit, border_columns_limit())
+
+
+def link_solver(A):
+    """``LinkedRowsNormalSolver`` for a sparse A when the option is on, the split applies and the
+    solver neither refuses nor flags the Schur complement of the link rows as numerically
+    singular (``ill_conditioned``: the caller's other choices have their own exits for such a
+    matrix); else None."""
+    split = _link_split_for(A.pattern) if isinstance(A, DeviceCSR) else None
+    if split is None:
+        return None
+    from .linked import LinkedRowsNormalSolver, LinkedRefused
+    try:
+        solver = LinkedRowsNormalSolver(A, split)
+    except LinkedRefused:
+        return None
+    return None if solver.ill_conditioned else solver
+
+
 def solver_name(solver):
     """Class name of a normal-equation solver; ``Outer/Inner`` (recursively) for a solver that
-    sits on an inner one: the box-Schur elimination, the bordered solver."""
+    sits on an inner one: the box-Schur elimination, the bordered and the linked solver."""
     if solver is None:
         return None
     name = type(solver).__name__
@@ -772,7 +825,11 @@ def wide_band_inner(B):
     """The box-Schur elimination's inner solver for ``B B'`` of any sparsity under the policy
     in force: the block-tridiagonal solver when the policy asks for it and the half bandwidth
     allows it, else None (the caller's dense / iterative choice).  With border columns allowed
-    (``border_columns``) the bordered solver comes first."""
+    (``border_columns``) the bordered solver comes first, and with link rows allowed
+    (``link_rows``) the linked solver before it."""
+    solver = link_solver(B)
+    if solver is not None:
+        return solver
     solver = bordered_solver(B)
     if solver is not None:
         return solver
@@ -797,6 +854,21 @@ def _pick_normal_solver(A, deferred=None):
         return DenseNormalSolver(A)
     kmax = _hip.load().ipx_banded_kmax()
     m = A.shape[0]
+    if link_rows_limit() > 0:
+        # a band plus a few dense rows (linked.py), before everything else; a refusal in either
+        # place goes on with the order below
+        solver = link_solver(A)                                            # (L1)
+        if solver is not None:
+            return solver
+        if _box_schur_applies(A, kmax, any_sparsity=True) \
+                and _link_split_for(_general_rows(A).pattern) is not None:
+            # (L2) bound rows eliminated in closed form; the general rows are such a matrix (a
+            # linking inequality of a barrier problem with a box)
+            from .boxschur import BoxSchurNormalSolver
+            from .linked import LinkedRowsNormalSolver
+            solver = BoxSchurNormalSolver(A, any_sparsity=True)
+            if isinstance(solver.inner, LinkedRowsNormalSolver):
+                return solver
     if border_columns_limit() > 0:
         # a band plus a few dense columns (bordered.py), before everything else; a refusal in
         # either place goes on with the order below
@@ -881,6 +953,8 @@ def _banded_row_order(A):
         return None
     if _border_split_for(A.pattern) is not None:
         return None             # (the bordered solver's band has its own order; A A' is full)
+    if _link_split_for(A.pattern) is not None:
+        return None             # (likewise the linked solver's)
     sym = _symbolic_for(A.pattern)
     return sym.perm if (sym.k <= kmax and sym.perm is not None) else None
 
@@ -917,7 +991,8 @@ def projections(A, method=None, orth_tol=1e-12, max_refin=3, tol=1e-15, deferred
     # reference to the tensor it was made for: a reassigned ``A.val`` can then never collide
     # with a collected tensor's id.
     t, version = _values_version(A)
-    key = (method, orth_tol, max_refin, tol, version, wide_band_policy(), border_columns_limit())
+    key = (method, orth_tol, max_refin, tol, version, wide_band_policy(), border_columns_limit(),
+           link_rows_limit())
     cached = getattr(A, "_ipx_projections", None)
     if cached is not None and version is not None and cached[0] == key and cached[2] is t:
         # (a caller that cannot take a pending verdict along gets it settled first)
@@ -1010,3 +1085,4 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
 
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: E402,F401  (public here)
 from .bordered import BorderedNormalSolver, BorderedRefused, border_split  # noqa: E402,F401
+from .linked import LinkedRowsNormalSolver, LinkedRefused, link_split  # noqa: E402,F401

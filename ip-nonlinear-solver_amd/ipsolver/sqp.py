@@ -418,9 +418,9 @@ def _settle_key(pt, method):
     tens = (getattr(pt.A, "val", None), getattr(pt.c, "t", None), getattr(pt.b, "t", None))
     if any(t is None or not hasattr(t, "_version") for t in tens):
         return None
-    # (a factorization belongs to its policy and its border-column limit)
-    from .projector import wide_band_policy, border_columns_limit
-    return ((method, wide_band_policy(), border_columns_limit()),) \
+    # (a factorization belongs to its policy, its border-column limit and its link-row limit)
+    from .projector import wide_band_policy, border_columns_limit, link_rows_limit
+    return ((method, wide_band_policy(), border_columns_limit(), link_rows_limit()),) \
         + tuple((t, t._version) for t in tens)
 
 
