@@ -892,6 +892,24 @@ int ipx_blocktri_factor(int64_t m, int32_t b, const double *D, const double *E, 
 int ipx_blocktri_solve(int64_t m, int32_t b, double *ws, const double *w, double *x,
                        void *stream);
 
+/* ---- the same for half bandwidths past ipx_blocktri_kmax() up to ipx_blockwide_kmax() = 256
+ * (csrc/blocktri.hip, second part): blocks of b = 128 or 256 (anything else: IPX_EINVAL), worked
+ * on as tiles of 64 x 64 in global memory.  Storage, pivot signals and every contract as for the
+ * ipx_blocktri_* calls above, `ws` holding ipx_blockwide_ws_doubles(m, b) doubles. */
+int ipx_blockwide_kmax(void);
+int64_t ipx_blockwide_ws_doubles(int64_t m, int32_t b);
+/* out[0] = levels of the reduction, out[1] = 1 (there is no one-workgroup tail: every level is
+ * launched on its own); returns out[0] - 1, or IPX_EINVAL.  Launches: factor 2 + 3 x that,
+ * solve 2 + 2 x that. */
+int ipx_blockwide_levels(int64_t m, int32_t b, int32_t out[2]);
+int ipx_aat_blockwide(int64_t m, int32_t b, int32_t k, const int32_t *rowptr,
+                      const int32_t *colidx, const double *val, const int32_t *perm, double *D,
+                      double *E, void *stream);
+int ipx_blockwide_factor(int64_t m, int32_t b, const double *D, const double *E, double *ws,
+                         int *flag, void *stream);
+int ipx_blockwide_solve(int64_t m, int32_t b, double *ws, const double *w, double *x,
+                        void *stream);
+
 /* ---- bordered direct solve with S = A A' (csrc/bordered.hip): A = [B | C], C the p dense columns
  * (1 <= p <= ipx_border_pmax() = 32), S = S_B + C C' by the Woodbury identity on top of a direct
  * solve with S_B = B B':  S^-1 w = u - Y z,  u = S_B^-1 w,  Y = S_B^-1 C,  K = I + C' Y,

@@ -139,6 +139,11 @@ _SIGNATURES = {
     "ipx_aat_blocktri": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
     "ipx_blocktri_factor": [_I64, _I32, _P, _P, _P, _P, _P],
     "ipx_blocktri_solve": [_I64, _I32, _P, _P, _P, _P],
+    "ipx_blockwide_kmax": [],
+    "ipx_blockwide_levels": [_I64, _I32, _P],
+    "ipx_aat_blockwide": [_I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "ipx_blockwide_factor": [_I64, _I32, _P, _P, _P, _P, _P],
+    "ipx_blockwide_solve": [_I64, _I32, _P, _P, _P, _P],
     "ipx_border_pmax": [],
     "ipx_border_rows_per_group": [],
     "ipx_border_groups": [_I64],
@@ -165,8 +170,10 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_lowrank_state_doubles": _I64, "ipx_lowrank_part_doubles": _I64,
              "ipx_lowrank_middle_host": None, "ipx_fd_steps_host": None,
              "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None,
-             "ipx_fd_assemble_sym_host": None, "ipx_blocktri_ws_doubles": _I64}
+             "ipx_fd_assemble_sym_host": None, "ipx_blocktri_ws_doubles": _I64,
+             "ipx_blockwide_ws_doubles": _I64}
 _EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
+                   "ipx_blockwide_ws_doubles": [_I64, _I32],
                    "ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
                    "ipx_dense_padded": [_I64], "ipx_gram_ws_doubles": [_I64, _I32],
                    "ipx_peer_create": [_I32, _I32, _I64],

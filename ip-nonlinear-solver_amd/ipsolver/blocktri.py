@@ -32,18 +32,23 @@ def block_size(k):
 class BlockTridiagonalNormalSolver:
     """(A A')^-1 by block cyclic reduction; pivot blocks applied as triangular factors."""
 
+    _ABI = "blocktri"       # the entry points are ipx_<_ABI>_factor, ipx_aat_<_ABI>, ...
+    _NAME = "block-tridiagonal"
+    _block_size = staticmethod(block_size)
+
     def __init__(self, A):
         from .projector import _symbolic_for
         lib = _hip.load()
+        abi = self._ABI
         sym = _symbolic_for(A.pattern)
-        kmax = lib.ipx_blocktri_kmax()
+        kmax = getattr(lib, "ipx_%s_kmax" % abi)()
         if sym.k > kmax:
             raise NotImplementedError(
-                "A A' has half bandwidth %d after reordering; the block-tridiagonal solver "
-                "handles <= %d" % (sym.k, kmax))
+                "A A' has half bandwidth %d after reordering; the %s solver "
+                "handles <= %d" % (sym.k, self._NAME, kmax))
         self.m = sym.m
         self.k = max(sym.k, 1)
-        self.b = block_size(self.k)
+        self.b = self._block_size(self.k)
         dev = ctx().device
         self.perm = None
         if sym.perm is not None:
@@ -54,17 +59,17 @@ class BlockTridiagonalNormalSolver:
         m, b = self.m, self.b
         nblk = -(-m // b)
         # one tensor owns everything the factorization and the solves use (include/ipx.h)
-        self.ws = torch.empty(int(lib.ipx_blocktri_ws_doubles(m, b)), dtype=torch.float64,
-                              device=dev)
+        self.ws = torch.empty(int(getattr(lib, "ipx_%s_ws_doubles" % abi)(m, b)),
+                              dtype=torch.float64, device=dev)
         flag = torch.zeros(2, dtype=torch.int32, device=dev)
         D = ctypes.c_void_p(self.ws.data_ptr())
         E = ctypes.c_void_p(self.ws.data_ptr() + 8 * nblk * b * b)
         p = A.pattern
-        _hip.call("ipx_aat_blocktri", m, b, self.k, _p(p.indptr), _p(p.indices), _p(A.val),
+        _hip.call("ipx_aat_%s" % abi, m, b, self.k, _p(p.indptr), _p(p.indices), _p(A.val),
                   _p(self.perm), D, E, stream_ptr())
-        _hip.call("ipx_blocktri_factor", m, b, D, E, _p(self.ws), _p(flag), stream_ptr())
+        _hip.call("ipx_%s_factor" % abi, m, b, D, E, _p(self.ws), _p(flag), stream_ptr())
         geo = (ctypes.c_int32 * 2)()
-        self.level_launches = int(_hip.call("ipx_blocktri_levels", m, b, geo))
+        self.level_launches = int(_hip.call("ipx_%s_levels" % abi, m, b, geo))
         bits = int(flag[0].item())
         if bits & 4:
             raise np.linalg.LinAlgError("Singular Jacobian matrix: A A' is not positive definite")
@@ -84,7 +89,7 @@ class BlockTridiagonalNormalSolver:
         if self.perm is not None:
             w = self._gather(w, self.perm)
         out = dv._empty(self.m)
-        _hip.call("ipx_blocktri_solve", self.m, self.b, _p(self.ws), _p(w.t), _p(out),
+        _hip.call("ipx_%s_solve" % self._ABI, self.m, self.b, _p(self.ws), _p(w.t), _p(out),
                   stream_ptr())
         self.stats["solves"] += 1
         v = DVec(out)

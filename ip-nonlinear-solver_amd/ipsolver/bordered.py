@@ -6,8 +6,8 @@ parameters, a design variable shared by all stages.
 
     (S_B + C C')^-1 w = u - Y K^-1 Y' w,   u = S_B^-1 w,   Y = S_B^-1 C,   K = I_p + C' Y,
 
-one solve with the direct factorization of ``S_B = B B'`` (``BandedNormalSolver`` or
-``BlockTridiagonalNormalSolver``, unchanged) plus O(m p) work.  Opt-in:
+one solve with the direct factorization of ``S_B = B B'`` (``BandedNormalSolver``,
+``BlockTridiagonalNormalSolver`` or its wide form, unchanged) plus O(m p) work.  Opt-in:
 ``projector.border_columns(limit)``, ``options={"border_columns": limit}``.
 
 Error growth.  ``u - Y z`` cancels when ``C C'`` dominates ``S_B``: the backward error is
@@ -144,8 +144,7 @@ class BorderedNormalSolver:
     perm = None        # rows are taken in the caller's order
 
     def __init__(self, A, split):
-        from .projector import BandedNormalSolver, BandedNotDecoupled
-        from .blocktri import BlockTridiagonalNormalSolver
+        from .projector import BandedNotDecoupled, direct_solver_class
         from .device_mode import gather
         lib = _hip.load()
         self.A = A
@@ -153,8 +152,7 @@ class BorderedNormalSolver:
         pat, b_src, c_src, c_dst = split.on_device()
         B = DeviceCSR(pat, gather(A.val, b_src))
         try:
-            self.inner = BandedNormalSolver(B) if split.k <= lib.ipx_banded_kmax() \
-                else BlockTridiagonalNormalSolver(B)
+            self.inner = direct_solver_class(split.k)(B)
         except (np.linalg.LinAlgError, BandedNotDecoupled) as exc:
             raise BorderedRefused("bordered solver: the factorization of B B' failed (%s)" % exc)
         if getattr(self.inner, "ill_conditioned", False):

@@ -10,7 +10,8 @@ The rows of A are band rows B and q <= 32 link rows D, in any positions of the c
     Y = S_B^-1 E,   K = F - E' Y,   u = S_B^-1 w_B,   K z = w_D - Y' w_B,   v_B = u - Y z,  v_D = z,
 
 one solve with the direct factorization of ``S_B`` (``BorderedNormalSolver``,
-``BandedNormalSolver`` or ``BlockTridiagonalNormalSolver``, unchanged) plus O(m q) work.  Opt-in:
+``BandedNormalSolver``, ``BlockTridiagonalNormalSolver`` or its wide form, unchanged) plus O(m q)
+work.  Opt-in:
 ``projector.link_rows(limit)``, ``options={"link_rows": limit}``.
 
 This is a block Cholesky of an SPD matrix, not a Woodbury update: its error carries
@@ -162,19 +163,15 @@ def _link_rows(pattern, reach, limit, border):
 
 def _inner_solver(B):
     """The solver of B B' under the policy in force: the bordered solver when border columns are
-    allowed and B is such a matrix, the banded solver, the block-tridiagonal one."""
-    from .projector import (BandedNormalSolver, BandedNotDecoupled, bordered_solver,
-                            wide_band_policy, _symbolic_for)
-    from .blocktri import BlockTridiagonalNormalSolver
-    lib = _hip.load()
+    allowed and B is such a matrix, else ``projector.direct_solver_class``'s."""
+    from .projector import (BandedNotDecoupled, border_reach, bordered_solver,
+                            direct_solver_class, wide_band_policy, _symbolic_for)
     try:
         inner = bordered_solver(B)
         if inner is None:
             k = _symbolic_for(B.pattern).k
-            if k <= lib.ipx_banded_kmax():
-                inner = BandedNormalSolver(B)
-            elif wide_band_policy() == "block-tridiagonal" and k <= lib.ipx_blocktri_kmax():
-                inner = BlockTridiagonalNormalSolver(B)
+            if k <= border_reach():
+                inner = direct_solver_class(k)(B)
             else:
                 raise LinkedRefused("linked solver: B B' has half bandwidth %d, past the direct "
                                     "solvers under the policy %r" % (k, wide_band_policy()))

@@ -426,9 +426,9 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     """
     options = dict(options)
     # ADDITIVE option: which solver takes a sparse Jacobian whose A A' is banded past the banded
-    # kernels' half bandwidth ("iterative", the default, or "block-tridiagonal":
-    # projector.wide_band).  Held for the duration of the call -- every factorization of the
-    # run is made under it, not the first one only.
+    # kernels' half bandwidth ("iterative", the default, "block-tridiagonal" or
+    # "block-tridiagonal-wide": projector.wide_band).  Held for the duration of the call -- every
+    # factorization of the run is made under it, not the first one only.
     from . import projector
     policy = projector.check_wide_band(options.pop("wide_band", projector.wide_band_policy()))
     # ADDITIVE option: up to this many dense columns of a sparse Jacobian (global parameters of a

@@ -36,9 +36,11 @@ _F64 = torch.float64
 
 # ---- what takes a sparse A whose A A' is banded past the banded kernels' half bandwidth --------
 # "iterative" (default): the dense Cholesky while it fits, else the preconditioned CG;
-# "block-tridiagonal": block cyclic reduction (blocktri.py) up to half bandwidth 64.  Scoped:
-# ``with wide_band("block-tridiagonal"): ...``; part of the key of every cached factorization.
-WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal")
+# "block-tridiagonal": block cyclic reduction (blocktri.py) up to half bandwidth 64;
+# "block-tridiagonal-wide": the same, and blocks of 128 / 256 (blockwide.py) for half bandwidths
+# 65 ... 256.  Scoped: ``with wide_band("block-tridiagonal"): ...``; part of the key of every
+# cached factorization.
+WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide")
 _wide_band = ["iterative"]
 _last_solver = [None]
 
@@ -94,10 +96,30 @@ def border_columns(limit):
 
 
 def border_reach():
-    """The half bandwidth the band of a bordered matrix may have under the policy in force."""
+    """The largest half bandwidth of ``A A'`` that a direct band solver takes under the policy in
+    force (the banded solver's, the block-tridiagonal solver's, the wide one's): what the band of
+    a bordered or linked matrix may have."""
     lib = _hip.load()
-    return lib.ipx_blocktri_kmax() if wide_band_policy() == "block-tridiagonal" \
-        else lib.ipx_banded_kmax()
+    policy = wide_band_policy()
+    if policy == "block-tridiagonal-wide":
+        return lib.ipx_blockwide_kmax()
+    return lib.ipx_blocktri_kmax() if policy == "block-tridiagonal" else lib.ipx_banded_kmax()
+
+
+def direct_solver_class(k):
+    """The direct band solver for half bandwidth k: banded, block tridiagonal, or wide block
+    tridiagonal (which itself refuses k past ``ipx_blockwide_kmax()``).  The one place that maps
+    k to a class; whether the policy in force allows it is the caller's ``k <= border_reach()``
+    (``normal_solver_for``, ``wide_band_inner``, linked.py -- bordered.py is handed a split that
+    was made under that condition, or by a caller who chose the columns)."""
+    lib = _hip.load()
+    if k <= lib.ipx_banded_kmax():
+        return BandedNormalSolver
+    if k <= lib.ipx_blocktri_kmax():
+        from .blocktri import BlockTridiagonalNormalSolver
+        return BlockTridiagonalNormalSolver
+    from .blockwide import WideBlockTridiagonalNormalSolver
+    return WideBlockTridiagonalNormalSolver
 
 
 def _border_split_for(pattern):
@@ -833,12 +855,13 @@ def wide_band_inner(B):
     solver = bordered_solver(B)
     if solver is not None:
         return solver
-    if wide_band_policy() != "block-tridiagonal":
+    if wide_band_policy() == "iterative":
         return None
     from .blocktri import BlockTridiagonalNormalSolver
-    if _symbolic_for(B.pattern).k > _hip.load().ipx_blocktri_kmax():
-        return None
-    return BlockTridiagonalNormalSolver(B)
+    k = _symbolic_for(B.pattern).k
+    if k <= _hip.load().ipx_blocktri_kmax():
+        return BlockTridiagonalNormalSolver(B)      # (also what the banded kernels would take)
+    return direct_solver_class(k)(B) if k <= border_reach() else None
 
 
 def normal_solver_for(A, deferred=None):
@@ -885,10 +908,10 @@ def _pick_normal_solver(A, deferred=None):
                 return solver
     # the wide-band policy (see ``wide_band``): dense A and half bandwidths <= kmax keep their
     # order; three places differ, marked (W1)-(W3)
-    wide = wide_band_policy() == "block-tridiagonal"
+    wide = wide_band_policy() != "iterative"
     if wide:
         from .blocktri import BlockTridiagonalNormalSolver
-        bt_kmax = _hip.load().ipx_blocktri_kmax()
+        bt_kmax = border_reach()        # (64, or 256 under "block-tridiagonal-wide")
     if half_bandwidth_of_aat(A.pattern) > kmax and _box_schur_applies(A, kmax):
         # the barrier problem's augmented Jacobian: a general row couples with the two bound
         # rows of each of its variables, no reordering of A A' is narrow -- skip the attempt
@@ -928,7 +951,7 @@ def _pick_normal_solver(A, deferred=None):
             if wide:
                 return BoxSchurNormalSolver(A, any_sparsity=True)          # (W1)
     if wide and kmax < k <= bt_kmax:
-        return BlockTridiagonalNormalSolver(A)  # (W3) block cyclic reduction, any m
+        return direct_solver_class(k)(A)        # (W3) block cyclic reduction, any m
     if m <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
         return DenseNormalSolver(A)             # wide band: dense Cholesky of A A'
     if _box_schur_applies(A, kmax, any_sparsity=True):
@@ -1084,5 +1107,6 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
 
 
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: E402,F401  (public here)
+from .blockwide import WideBlockTridiagonalNormalSolver  # noqa: E402,F401  (public here)
 from .bordered import BorderedNormalSolver, BorderedRefused, border_split  # noqa: E402,F401
 from .linked import LinkedRowsNormalSolver, LinkedRefused, link_split  # noqa: E402,F401
