@@ -14,6 +14,7 @@ import torch
 
 from . import _hip
 from . import device as dv
+from .banded import _symbolic_for
 from .device import DVec, _p, stream_ptr, ctx
 
 BLOCK_SIZES = (16, 32, 64)     # (the largest is ipx_blocktri_kmax())
@@ -37,7 +38,6 @@ class BlockTridiagonalNormalSolver:
     _block_size = staticmethod(block_size)
 
     def __init__(self, A):
-        from .projector import _symbolic_for
         lib = _hip.load()
         abi = self._ABI
         sym = _symbolic_for(A.pattern)

@@ -22,7 +22,11 @@ import torch
 
 from . import _hip
 from . import device as dv
+from .band_solver import border_reach, direct_band_solver
+from .banded import BandedNotDecoupled, HostPattern, _symbolic_for, share_analysis  # noqa: F401
 from .device import DVec, DeviceCSR, CSRPattern, _p, stream_ptr, ctx
+from .device_mode import gather
+from .solver_options import current
 
 # eta ~ c kappa_B kappa(K) u with c of order 1 and the projector's orth_tol = 1e-12 ~ 2^13 u:
 # up to trace(K) = 2^10 a well-conditioned S_B (kappa_B <= 8) stays below orth_tol without help;
@@ -35,16 +39,6 @@ GROWTH_MAX = 2.0 ** 26
 class BorderedRefused(NotImplementedError):
     """The bordered solver declines this matrix (inner factorization failed or ill-conditioned,
     or trace(K) past GROWTH_MAX): the caller goes on with its other solvers."""
-
-
-class HostPattern:
-    """What the symbolic analysis (projector._Symbolic) reads of a pattern, on the host."""
-
-    def __init__(self, indptr, indices, shape):
-        self.indptr_h = np.ascontiguousarray(indptr, dtype=np.int32)
-        self.indices_h = np.ascontiguousarray(indices, dtype=np.int32)
-        self.shape = (int(shape[0]), int(shape[1]))
-        self.nnz = int(self.indptr_h[-1])
 
 
 class BorderSplit:
@@ -61,18 +55,16 @@ class BorderSplit:
     @property
     def k(self):
         """half bandwidth of B B' (after B's own reordering)"""
-        from .projector import _symbolic_for
         return _symbolic_for(self.host).k
 
     def on_device(self):
         """(B's CSRPattern carrying the symbolic analysis made on the host, b_src, c_src,
         c_dst as device tensors)"""
         if self._dev is None:
-            from .projector import _SYMBOLIC_ATTR, _symbolic_for
             dev = ctx().device
-            pat = CSRPattern(self.host.indptr_h, self.host.indices_h, self.host.shape)
-            setattr(pat, _SYMBOLIC_ATTR, _symbolic_for(self.host))
-            pat._ipx_aat_half_bw = self.host._ipx_aat_half_bw
+            _symbolic_for(self.host)
+            pat = share_analysis(self.host, CSRPattern(self.host.indptr_h, self.host.indices_h,
+                                                       self.host.shape))
             to = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, dtype=t)).to(dev)
             assert len(self.c_dst) == 0 or (0 <= self.c_dst.min()
                                             and self.c_dst.max() < self.m * self.p)
@@ -144,15 +136,13 @@ class BorderedNormalSolver:
     perm = None        # rows are taken in the caller's order
 
     def __init__(self, A, split):
-        from .projector import BandedNotDecoupled, direct_solver_class
-        from .device_mode import gather
         lib = _hip.load()
         self.A = A
         self.m, self.p = m, p = split.m, split.p
         pat, b_src, c_src, c_dst = split.on_device()
         B = DeviceCSR(pat, gather(A.val, b_src))
         try:
-            self.inner = direct_solver_class(split.k)(B)
+            self.inner = direct_band_solver(B, whatever_the_policy=True)
         except (np.linalg.LinAlgError, BandedNotDecoupled) as exc:
             raise BorderedRefused("bordered solver: the factorization of B B' failed (%s)" % exc)
         if getattr(self.inner, "ill_conditioned", False):
@@ -200,3 +190,23 @@ class BorderedNormalSolver:
             self.stats["refinements"] += 1
         self.stats["solves"] += 1
         return v
+
+
+def _border_split_for(pattern):
+    """The border split of a pattern under the options in force, or None (also: option off)."""
+    limit = current().border_columns
+    if limit < 1:
+        return None
+    return border_split(pattern, border_reach(), limit)
+
+
+def bordered_solver(A):
+    """``BorderedNormalSolver`` for a sparse A when the option is on, the split applies and the
+    solver does not refuse; else None (the caller's other choices)."""
+    split = _border_split_for(A.pattern) if isinstance(A, DeviceCSR) else None
+    if split is None:
+        return None
+    try:
+        return BorderedNormalSolver(A, split)
+    except BorderedRefused:
+        return None

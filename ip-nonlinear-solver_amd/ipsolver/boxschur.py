@@ -22,7 +22,14 @@ import torch
 
 from . import _hip
 from . import device as dv
+from .band_solver import direct_band_solver
+from .banded import BandedNormalSolver, HostPattern, share_analysis
+from .bordered import bordered_solver
+from .dense import DenseNormalSolver
 from .device import DVec, _p, stream_ptr, ctx
+from .device_mode import RowSelection
+from .iterative import IterativeNormalSolver
+from .linked import link_solver
 
 _F64 = torch.float64
 
@@ -86,6 +93,48 @@ def analysis_for(pattern):
     return a
 
 
+def general_rows_pattern(pattern):
+    """Pattern of the rows the elimination leaves to its inner solver, for the selection's
+    pattern tests: the device selection's when there is one, else a host pattern (made once per
+    pattern, cached on it) -- so the rows are analysed once, on whichever came first."""
+    sel = getattr(pattern, "_ipx_box_general_pattern", None)
+    if sel is not None:
+        return sel.pattern
+    host = getattr(pattern, "_ipx_box_general_host", None)
+    if host is None:
+        rows = analysis_for(pattern).general
+        indptr, counts, start = RowSelection.row_pointers(pattern, rows)
+        src = np.repeat(indptr[rows] - start[:-1], counts) + np.arange(int(start[-1]))
+        host = pattern._ipx_box_general_host = HostPattern(
+            start, pattern.indices_h[src], (len(rows), pattern.shape[1]))
+    return host
+
+
+def general_rows(pattern):
+    """The selection of those rows on the device (once per pattern); its pattern takes over
+    whatever analysis the host pattern has by then, and ``general_rows_pattern`` returns it from
+    then on."""
+    sel = getattr(pattern, "_ipx_box_general_pattern", None)
+    if sel is None:
+        sel = RowSelection(pattern, analysis_for(pattern).general, None)
+        host = getattr(pattern, "_ipx_box_general_host", None)
+        if host is not None:
+            share_analysis(host, sel.pattern)
+        pattern._ipx_box_general_pattern = sel
+    return sel
+
+
+def wide_band_inner(B):
+    """The elimination's inner solver for ``B B'`` of any sparsity under the options in force,
+    or None (the caller's dense / iterative choice): the linked solver where link rows are allowed
+    and B is such a matrix, then the bordered solver likewise, then the direct band solver the
+    wide-band policy allows (``direct_band_solver``; the banded solver is not offered)."""
+    solver = link_solver(B)
+    if solver is None:
+        solver = bordered_solver(B)
+    return solver if solver is not None else direct_band_solver(B, banded_has_refused=True)
+
+
 _P, _I64 = ctypes.c_void_p, ctypes.c_int64
 
 
@@ -110,16 +159,12 @@ class BoxSchurNormalSolver:
     banded solve on the Schur complement of the general rows."""
 
     def __init__(self, A, any_sparsity=False):
-        from .device_mode import RowSelection
-        from .projector import BandedNormalSolver
         an = analysis_for(A.pattern)
         self.an, self.m, self.n = an, an.m, an.n
         pat = A.pattern
         cache = getattr(pat, "_ipx_box_device", None)
         if cache is None:
-            sel = getattr(pat, "_ipx_box_general_pattern", None) or RowSelection(pat, an.general,
-                                                                                None)
-            pat._ipx_box_general_pattern = sel
+            sel = general_rows(pat)
             # tables of ipx_boxschur_project: per group the shared column and the rows' private
             # columns; the columns outside every group
             idx = pat.indices_h
@@ -165,9 +210,7 @@ class BoxSchurNormalSolver:
         if any_sparsity:
             # Sigma = A_R W A_R' = B B' with B = A_R diag(sqrt(w)) (0 < w <= 1): a scaled copy of
             # the general rows' values goes to the solver of any sparsity -- dense Cholesky up to
-            # 16384 rows, else the device-resident preconditioned CG (projector.py section 4)
-            from .projector import IterativeNormalSolver
-            from .dense import DenseNormalSolver
+            # 16384 rows, else the device-resident preconditioned CG (iterative.py)
             sw = torch.sqrt(self.wcol)
             idx = getattr(self.A_R.pattern, "_ipx_col_index64", None)
             if idx is None:
@@ -175,8 +218,7 @@ class BoxSchurNormalSolver:
             B = dv.DeviceCSR(self.A_R.pattern, self.A_R.val * sw[idx])
             self.B = B
             mR = B.shape[0]
-            # (the wide-band policy, projector.wide_band: block cyclic reduction when asked for)
-            from .projector import wide_band_inner
+            # (the wide-band policy: block cyclic reduction when asked for)
             self.inner = wide_band_inner(B)
             if self.inner is None:
                 self.inner = DenseNormalSolver(B) \

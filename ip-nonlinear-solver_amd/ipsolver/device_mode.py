@@ -104,10 +104,16 @@ class RowSelection:
     """J[rows, :] scaled by ``sign`` per row, as a value refresh on a pattern
     derived once from J's pattern (_canonical_constraint.py:251-265)."""
 
-    def __init__(self, pattern, rows, sign):
-        indptr, indices = pattern.indptr_h.astype(np.int64), pattern.indices_h
+    @staticmethod
+    def row_pointers(pattern, rows):
+        """(row starts of the pattern, entries per selected row, row pointers of the selection)"""
+        indptr = pattern.indptr_h.astype(np.int64)
         counts = indptr[rows + 1] - indptr[rows]
-        new_indptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+        return indptr, counts, np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+
+    def __init__(self, pattern, rows, sign):
+        indices = pattern.indices_h
+        indptr, counts, new_indptr = self.row_pointers(pattern, rows)
         self.identity = (len(rows) == pattern.shape[0]
                          and np.array_equal(rows, np.arange(pattern.shape[0]))
                          and (sign is None or np.all(sign == 1)))

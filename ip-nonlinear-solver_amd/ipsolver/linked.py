@@ -26,8 +26,12 @@ import torch
 
 from . import _hip
 from . import device as dv
-from .bordered import HostPattern
+from .band_solver import border_reach, direct_band_solver
+from .banded import BandedNotDecoupled, HostPattern, _symbolic_for, share_analysis
+from .bordered import bordered_solver
 from .device import DeviceCSR, CSRPattern, _p, stream_ptr, ctx
+from .device_mode import gather
+from .solver_options import current
 
 
 class LinkedRefused(NotImplementedError):
@@ -55,18 +59,16 @@ class LinkSplit:
     @property
     def k(self):
         """half bandwidth of B B' (after B's own reordering)"""
-        from .projector import _symbolic_for
         return _symbolic_for(self.host).k
 
     def on_device(self):
         """(B's CSRPattern carrying the symbolic analysis made on the host, then b_src, c_src,
         c_dst, b_rows, d_rows, dst_row as device tensors)"""
         if self._dev is None:
-            from .projector import _SYMBOLIC_ATTR, _symbolic_for
             dev = ctx().device
-            pat = CSRPattern(self.host.indptr_h, self.host.indices_h, self.host.shape)
-            setattr(pat, _SYMBOLIC_ATTR, _symbolic_for(self.host))
-            pat._ipx_aat_half_bw = self.host._ipx_aat_half_bw
+            _symbolic_for(self.host)
+            pat = share_analysis(self.host, CSRPattern(self.host.indptr_h, self.host.indices_h,
+                                                       self.host.shape))
             to = lambda a, t: torch.from_numpy(np.ascontiguousarray(a, dtype=t)).to(dev)
             assert len(self.c_dst) == 0 or (0 <= self.c_dst.min()
                                             and self.c_dst.max() < self.n * self.q)
@@ -163,18 +165,15 @@ def _link_rows(pattern, reach, limit, border):
 
 def _inner_solver(B):
     """The solver of B B' under the policy in force: the bordered solver when border columns are
-    allowed and B is such a matrix, else ``projector.direct_solver_class``'s."""
-    from .projector import (BandedNotDecoupled, border_reach, bordered_solver,
-                            direct_solver_class, wide_band_policy, _symbolic_for)
+    allowed and B is such a matrix, else ``band_solver.direct_band_solver``'s."""
     try:
         inner = bordered_solver(B)
         if inner is None:
-            k = _symbolic_for(B.pattern).k
-            if k <= border_reach():
-                inner = direct_solver_class(k)(B)
-            else:
-                raise LinkedRefused("linked solver: B B' has half bandwidth %d, past the direct "
-                                    "solvers under the policy %r" % (k, wide_band_policy()))
+            inner = direct_band_solver(B)
+        if inner is None:
+            raise LinkedRefused("linked solver: B B' has half bandwidth %d, past the direct "
+                                "solvers under the policy %r"
+                                % (_symbolic_for(B.pattern).k, current().wide_band))
     except (np.linalg.LinAlgError, BandedNotDecoupled) as exc:
         raise LinkedRefused("linked solver: the factorization of B B' failed (%s)" % exc)
     if getattr(inner, "ill_conditioned", False):
@@ -192,7 +191,6 @@ class LinkedRowsNormalSolver:
     perm = None        # rows come and go in the caller's order
 
     def __init__(self, A, split):
-        from .device_mode import gather
         lib = _hip.load()
         self.A = A
         self.m, self.n, self.q, self.m_b = m, n, q, mB = split.m, split.n, split.q, split.m_b
@@ -224,7 +222,6 @@ class LinkedRowsNormalSolver:
 
     def solve(self, w):
         """v = (A A')^-1 w, in the caller's row order."""
-        from .device_mode import gather
         m, q = self.m, self.q
         w_b = self._wb[:self.m_b]                            # (the q entries past it stay zero)
         gather(w.t, self._b_rows, out=w_b)
@@ -236,3 +233,26 @@ class LinkedRowsNormalSolver:
         self.stats["solves"] += 1
         self.stats["inner_solves"] += 1
         return dv._wrap(v)
+
+
+def _link_split_for(pattern):
+    """The link split of a pattern under the options in force, or None (also: option off)."""
+    limit = current().link_rows
+    if limit < 1:
+        return None
+    return link_split(pattern, border_reach(), limit, current().border_columns)
+
+
+def link_solver(A):
+    """``LinkedRowsNormalSolver`` for a sparse A when the option is on, the split applies and the
+    solver neither refuses nor flags the Schur complement of the link rows as numerically
+    singular (``ill_conditioned``: the caller's other choices have their own exits for such a
+    matrix); else None."""
+    split = _link_split_for(A.pattern) if isinstance(A, DeviceCSR) else None
+    if split is None:
+        return None
+    try:
+        solver = LinkedRowsNormalSolver(A, split)
+    except LinkedRefused:
+        return None
+    return None if solver.ill_conditioned else solver

@@ -17,6 +17,7 @@ import numpy as np
 from scipy.optimize import OptimizeResult
 
 from . import backend as _backend
+from . import solver_options
 from .barrier import tr_interior_point
 from .canonical import (lagrangian_hessian, to_canonical, empty_canonical_constraint,
                         HessianSum)
@@ -425,24 +426,15 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
     partitioned over the ranks (ipsolver/sharded.py), the result carries global arrays.
     """
     options = dict(options)
-    # ADDITIVE option: which solver takes a sparse Jacobian whose A A' is banded past the banded
-    # kernels' half bandwidth ("iterative", the default, "block-tridiagonal" or
-    # "block-tridiagonal-wide": projector.wide_band).  Held for the duration of the call -- every
-    # factorization of the run is made under it, not the first one only.
+    # ADDITIVE options: which solver takes a sparse Jacobian whose A A' is a band past the banded
+    # kernels' half bandwidth, or such a band but for a few dense columns (global parameters of a
+    # staged problem) or dense rows (its linking constraints) -- solver_options.py has the names,
+    # values and defaults.  Checked before anything runs and held for the duration of the call:
+    # every factorization of the run is made under them, not the first one only.
     from . import projector
-    policy = projector.check_wide_band(options.pop("wide_band", projector.wide_band_policy()))
-    # ADDITIVE option: up to this many dense columns of a sparse Jacobian (global parameters of a
-    # staged problem) are split off as a border of a banded / block-tridiagonal A A'
-    # (projector.border_columns, bordered.py); 0, the default: off.  Held like the policy.
-    border = projector.check_border_columns(
-        options.pop("border_columns", projector.border_columns_limit()))
-    # ADDITIVE option: up to this many dense rows of a sparse Jacobian (linking constraints of a
-    # staged problem: a budget, a periodicity condition) are split off from a banded /
-    # block-tridiagonal A A' (projector.link_rows, linked.py); 0, the default: off.
-    link = projector.check_link_rows(options.pop("link_rows", projector.link_rows_limit()))
+    held = solver_options.pop_from(options)
     projector._last_solver[0] = None
-    with projector.wide_band(policy), projector.border_columns(border), \
-            projector.link_rows(link):
+    with solver_options.scoped(**held):
         result = _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol,
                                        sparse_jacobian, options, callback, max_iter, verbose)
     # the solver behind the projections the run was handed last, made then or reused from a

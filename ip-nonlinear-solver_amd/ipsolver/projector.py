@@ -22,7 +22,6 @@ matvecs (``SVDProjector``).
 """
 from warnings import warn
 
-import contextlib
 import ctypes
 
 import numpy as np
@@ -30,187 +29,32 @@ import torch
 
 from . import _hip
 from . import device as dv
+from . import solver_options
 from .device import DVec, DeviceCSR, _p, stream_ptr, ctx
+from .dense import DenseNormalSolver, DeviceDense
+from .device_mode import RowSelection
+# The solvers, their selection and its options live in modules of their own, layered
+#   solver_options < banded < blocktri, blockwide, iterative < band_solver < bordered < linked
+#   < boxschur < selection < this one;
+# their names stay public here.
+from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link_rows,  # noqa: F401
+                             wide_band_policy, border_columns_limit, link_rows_limit,
+                             check_wide_band, check_border_columns, check_link_rows)
+from .banded import (BandedNormalSolver, BandedNotDecoupled, HANDLE_STATS, _Symbolic,  # noqa: F401
+                     _SYMBOLIC_ATTR, _symbolic_for, half_bandwidth_of_aat)
+from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: F401
+from .blockwide import WideBlockTridiagonalNormalSolver  # noqa: F401
+from .iterative import IterativeNormalSolver, PcgArgs  # noqa: F401
+from .band_solver import border_reach, direct_band_solver, direct_solver_class  # noqa: F401
+from .bordered import (BorderedNormalSolver, BorderedRefused, border_split,  # noqa: F401
+                       bordered_solver, _border_split_for)
+from .linked import (LinkedRowsNormalSolver, LinkedRefused, link_split, link_solver,  # noqa: F401
+                     _link_split_for)
+from .boxschur import BoxSchurNormalSolver, wide_band_inner  # noqa: F401
+from .selection import (normal_solver_for, solver_name, last_normal_solver,  # noqa: F401
+                        _last_solver, _pick_normal_solver, _banded_row_order)
 
 _F64 = torch.float64
-
-# ---- what takes a sparse A whose A A' is banded past the banded kernels' half bandwidth --------
-# "iterative" (default): the dense Cholesky while it fits, else the preconditioned CG;
-# "block-tridiagonal": block cyclic reduction (blocktri.py) up to half bandwidth 64;
-# "block-tridiagonal-wide": the same, and blocks of 128 / 256 (blockwide.py) for half bandwidths
-# 65 ... 256.  Scoped: ``with wide_band("block-tridiagonal"): ...``; part of the key of every
-# cached factorization.
-WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide")
-_wide_band = ["iterative"]
-_last_solver = [None]
-
-
-def check_wide_band(policy):
-    if policy not in WIDE_BAND_POLICIES:
-        raise ValueError("wide_band must be one of %s, not %r"
-                         % (", ".join(repr(p) for p in WIDE_BAND_POLICIES), policy))
-    return policy
-
-
-def wide_band_policy():
-    return _wide_band[0]
-
-
-@contextlib.contextmanager
-def wide_band(policy):
-    """Hold the wide-band policy for the duration of the block (restored on any exit)."""
-    previous, _wide_band[0] = _wide_band[0], check_wide_band(policy)
-    try:
-        yield
-    finally:
-        _wide_band[0] = previous
-
-
-# ---- dense columns on top of a band (bordered.py) -------------------------------------------
-# Up to this many columns of a sparse A may be split off as a border when the rest is banded /
-# block tridiagonal in A A' (0, the default: off, every path as without the option).  Scoped like
-# the wide-band policy -- ``with border_columns(4): ...`` -- and part of the same cache keys.
-_border = [0]
-
-
-def check_border_columns(limit):
-    pmax = _hip.load().ipx_border_pmax()
-    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) \
-            or not 0 <= limit <= pmax:
-        raise ValueError("border_columns must be an integer in 0 ... %d, not %r" % (pmax, limit))
-    return int(limit)
-
-
-def border_columns_limit():
-    return _border[0]
-
-
-@contextlib.contextmanager
-def border_columns(limit):
-    """Hold the border-column limit for the duration of the block (restored on any exit)."""
-    previous, _border[0] = _border[0], check_border_columns(limit)
-    try:
-        yield
-    finally:
-        _border[0] = previous
-
-
-def border_reach():
-    """The largest half bandwidth of ``A A'`` that a direct band solver takes under the policy in
-    force (the banded solver's, the block-tridiagonal solver's, the wide one's): what the band of
-    a bordered or linked matrix may have."""
-    lib = _hip.load()
-    policy = wide_band_policy()
-    if policy == "block-tridiagonal-wide":
-        return lib.ipx_blockwide_kmax()
-    return lib.ipx_blocktri_kmax() if policy == "block-tridiagonal" else lib.ipx_banded_kmax()
-
-
-def direct_solver_class(k):
-    """The direct band solver for half bandwidth k: banded, block tridiagonal, or wide block
-    tridiagonal (which itself refuses k past ``ipx_blockwide_kmax()``).  The one place that maps
-    k to a class; whether the policy in force allows it is the caller's ``k <= border_reach()``
-    (``normal_solver_for``, ``wide_band_inner``, linked.py -- bordered.py is handed a split that
-    was made under that condition, or by a caller who chose the columns)."""
-    lib = _hip.load()
-    if k <= lib.ipx_banded_kmax():
-        return BandedNormalSolver
-    if k <= lib.ipx_blocktri_kmax():
-        from .blocktri import BlockTridiagonalNormalSolver
-        return BlockTridiagonalNormalSolver
-    from .blockwide import WideBlockTridiagonalNormalSolver
-    return WideBlockTridiagonalNormalSolver
-
-
-def _border_split_for(pattern):
-    from .bordered import border_split
-    limit = border_columns_limit()
-    if limit < 1:
-        return None
-    return border_split(pattern, border_reach(), limit)
-
-
-def bordered_solver(A):
-    """``BorderedNormalSolver`` for a sparse A when the option is on, the split applies and the
-    solver does not refuse; else None (the caller's other choices)."""
-    split = _border_split_for(A.pattern) if isinstance(A, DeviceCSR) else None
-    if split is None:
-        return None
-    from .bordered import BorderedNormalSolver, BorderedRefused
-    try:
-        return BorderedNormalSolver(A, split)
-    except BorderedRefused:
-        return None
-
-
-# ---- dense rows on top of a band (linked.py) -------------------------------------------------
-# Up to this many rows of a sparse A may be split off as link rows when the rest is banded / block
-# tridiagonal in A A' (0, the default: off, every path as without the option).  Scoped like the
-# border-column limit -- ``with link_rows(4): ...`` -- and part of the same cache keys.
-_link = [0]
-
-
-def check_link_rows(limit):
-    qmax = _hip.load().ipx_border_pmax()
-    if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) \
-            or not 0 <= limit <= qmax:
-        raise ValueError("link_rows must be an integer in 0 ... %d, not %r" % (qmax, limit))
-    return int(limit)
-
-
-def link_rows_limit():
-    return _link[0]
-
-
-@contextlib.contextmanager
-def link_rows(limit):
-    """Hold the link-row limit for the duration of the block (restored on any exit)."""
-    previous, _link[0] = _link[0], check_link_rows(limit)
-    try:
-        yield
-    finally:
-        _link[0] = previous
-
-
-def _link_split_for(pattern):
-    from .linked import link_split
-    limit = link_rows_limit()
-    if limit < 1:
-        return None
-    return link_split(pattern, border_reach(), limit, border_columns_limit())
-
-
-def link_solver(A):
-    """``LinkedRowsNormalSolver`` for a sparse A when the option is on, the split applies and the
-    solver neither refuses nor flags the Schur complement of the link rows as numerically
-    singular (``ill_conditioned``: the caller's other choices have their own exits for such a
-    matrix); else None."""
-    split = _link_split_for(A.pattern) if isinstance(A, DeviceCSR) else None
-    if split is None:
-        return None
-    from .linked import LinkedRowsNormalSolver, LinkedRefused
-    try:
-        solver = LinkedRowsNormalSolver(A, split)
-    except LinkedRefused:
-        return None
-    return None if solver.ill_conditioned else solver
-
-
-def solver_name(solver):
-    """Class name of a normal-equation solver; ``Outer/Inner`` (recursively) for a solver that
-    sits on an inner one: the box-Schur elimination, the bordered and the linked solver."""
-    if solver is None:
-        return None
-    name = type(solver).__name__
-    inner = getattr(solver, "inner", None)
-    return name if inner is None else "%s/%s" % (name, solver_name(inner))
-
-
-def last_normal_solver():
-    """``solver_name`` of the factorization ``projections`` handed out last, made then or taken
-    from its cache ("SVDProjector" for the SVD exit); None: none yet, or a Jacobian without
-    rows, which has nothing to factor."""
-    return _last_solver[0]
 
 
 def note_solver(ops):
@@ -219,193 +63,6 @@ def note_solver(ops):
         _last_solver[0] = solver_name(P.solver)
     else:
         _last_solver[0] = None if P is None else type(P).__name__
-
-
-def half_bandwidth_of_aat(pattern):
-    """Half bandwidth of ``A A'`` from the pattern of ``A`` alone, O(nnz): rows i and j couple
-    iff they share a column, so it is the widest (last row - first row) of a column.  (Forming
-    the product pattern for this, and trying a reordering of it, costs 0.1 s on the barrier
-    problem's 1e6-row augmented Jacobian, whose band no ordering makes narrow.)"""
-    k = getattr(pattern, "_ipx_aat_half_bw", None)
-    if k is None:
-        m, n = pattern.shape
-        rows = np.repeat(np.arange(m, dtype=np.int64), np.diff(pattern.indptr_h))
-        cols = pattern.indices_h
-        first, last = np.full(n, m, dtype=np.int64), np.full(n, -1, dtype=np.int64)
-        last[cols] = rows                      # rows ascend: the last write is the last row
-        first[cols[::-1]] = rows[::-1]         # ... and reversed, the first
-        used = last >= 0
-        k = int(np.max(last[used] - first[used])) if used.any() else 0
-        pattern._ipx_aat_half_bw = k
-    return k
-
-
-class _Symbolic:
-    """Pattern-level analysis of S = A A' (host, once per pattern)."""
-
-    def __init__(self, pattern):
-        import scipy.sparse as sps
-        from scipy.sparse.csgraph import reverse_cuthill_mckee
-        m, n = pattern.shape
-        ones = np.ones(pattern.nnz, dtype=np.float32)
-        B = sps.csr_matrix((ones, pattern.indices_h, pattern.indptr_h), shape=(m, n))
-        S = sps.csr_matrix(B.dot(B.T))
-        S.sort_indices()
-
-        def half_bw(M):
-            coo = M.tocoo()
-            return int(np.max(np.abs(coo.row - coo.col))) if coo.nnz else 0
-
-        self.k = half_bw(S)
-        assert self.k == half_bandwidth_of_aat(pattern), (self.k, half_bandwidth_of_aat(pattern))
-        self.perm = None
-        if self.k > 1 and m > 2:
-            perm = np.ascontiguousarray(reverse_cuthill_mckee(S, symmetric_mode=True),
-                                        dtype=np.int32)
-            k2 = half_bw(S[perm][:, perm])
-            if k2 < self.k:
-                self.k, self.perm = k2, perm
-        self.m = m
-
-    def __del__(self):
-        # handles parked by BandedNormalSolver for the next factorization on this pattern
-        for _, handle, _ in self.__dict__.get("_handle_pool", []):
-            try:
-                _hip.load().ipx_banded_destroy(ctypes.c_void_p(handle))
-            except Exception:
-                pass
-
-
-_SYMBOLIC_ATTR = "_ipx_aat_symbolic"
-
-
-def _symbolic_for(pattern):
-    sym = getattr(pattern, _SYMBOLIC_ATTR, None)
-    if sym is None:
-        sym = _Symbolic(pattern)
-        setattr(pattern, _SYMBOLIC_ATTR, sym)
-    return sym
-
-
-HANDLE_STATS = {"created": 0, "pooled": 0, "deferred": 0}     # banded handles (diagnostics)
-
-
-class BandedNotDecoupled(NotImplementedError):
-    """Half bandwidth 5..8 on a long band whose separator blocks do not decouple numerically
-    (csrc/banded.hip ipx_banded_create: there is no compiled separator level for them)."""
-
-
-class BandedNormalSolver:
-    """(A A')^-1 for sparse A with banded A A' (half bandwidth <= kmax)."""
-
-    def __init__(self, A, chunk=64, col_weights=None, deferred=None):
-        """``col_weights`` (device tensor, one per column of A) factors
-        ``A diag(w) A'`` instead (Schur complements, boxschur.py).  ``deferred`` (an object with
-        a device tensor ``verdict``: the outer iteration's chain, sqp_chain.py): the blocking
-        read that ends a factorization is left out when the handle's previous factorization was
-        clean -- the same verdict is assumed, a kernel checks it on the device
-        (``ipx_banded_status_deferred``) and the caller reads ``verdict`` with its next block
-        (``self.pending`` until then; ``confirm`` reads it on its own)."""
-        sym = _symbolic_for(A.pattern)
-        kmax = _hip.load().ipx_banded_kmax()
-        if sym.k > kmax:
-            raise NotImplementedError(
-                "A A' has half bandwidth %d after reordering; the device banded "
-                "solver handles <= %d (no host fallback)" % (sym.k, kmax))
-        self.m = sym.m
-        self.k = max(sym.k, 1)
-        dev = ctx().device
-        self.perm = None
-        if sym.perm is not None:
-            self.perm = torch.from_numpy(sym.perm).to(dev)          # new row i = old row perm[i]
-            inv = np.empty_like(sym.perm)
-            inv[sym.perm] = np.arange(self.m, dtype=np.int32)
-            self.iperm = torch.from_numpy(inv).to(dev)
-        # handle + band storage are recycled per pattern: creating / destroying a handle is a
-        # dozen hipMalloc / hipFree calls (~0.5 ms), more than the numeric refresh itself
-        lib = _hip.load()
-        self._sym = sym          # the pool's handles are destroyed with `sym`: keep it alive
-        self._pool = sym.__dict__.setdefault("_handle_pool", [])
-        self._key = (self.m, self.k, int(chunk))
-        self.handle, self.band = None, None
-        for i, (key, handle, band) in enumerate(self._pool):
-            if key == self._key:
-                self.handle, self.band = handle, band
-                del self._pool[i]
-                break
-        HANDLE_STATS["pooled" if self.handle is not None else "created"] += 1
-        if self.handle is None:
-            self.band = torch.empty((self.k + 1) * self.m, dtype=_F64, device=dev)
-            self.handle = lib.ipx_banded_create(self.m, self.k, int(chunk))
-            if not self.handle:
-                raise _hip.IpxError("ipx_banded_create failed (m=%d, k=%d)" % (self.m, self.k))
-        p = A.pattern
-        self.pending, self.ill_conditioned = False, False
-        if deferred is not None and self.perm is None and self.k == 1:
-            # the whole refresh behind one entry and in three launches where the handle
-            # qualifies (csrc/banded.hip ipx_banded_refactor); 0: it does not, nothing enqueued
-            rc = lib.ipx_banded_refactor(ctypes.c_void_p(self.handle), self.m, self.k,
-                                         _p(p.indptr), _p(p.indices), _p(A.val), _p(col_weights),
-                                         _p(self.band), deferred.verdict.data_ptr(), stream_ptr())
-            if rc < 0:
-                _hip.check(rc, "ipx_banded_refactor")
-            if rc == 1:
-                self.pending, self._verdict = True, deferred.verdict
-                HANDLE_STATS["deferred"] += 1
-                return
-        _hip.call("ipx_aat_band_w", self.m, self.k, _p(p.indptr), _p(p.indices), _p(A.val),
-                  _p(self.perm), _p(col_weights), _p(self.band), stream_ptr())
-        _hip.call("ipx_banded_factor", ctypes.c_void_p(self.handle), _p(self.band), stream_ptr())
-        if deferred is not None and lib.ipx_banded_status_deferred(
-                ctypes.c_void_p(self.handle), deferred.verdict.data_ptr(), stream_ptr()) == 0:
-            self.pending, self._verdict = True, deferred.verdict
-            HANDLE_STATS["deferred"] += 1
-            return
-        rc = lib.ipx_banded_status(ctypes.c_void_p(self.handle), stream_ptr())
-        if rc == -3:
-            raise np.linalg.LinAlgError("Singular Jacobian matrix: A A' is not positive definite")
-        # -6: every pivot positive but one lost 43 bits against its diagonal entry: numerically
-        # rank deficient.  ``projections`` takes the reference's SVD exit when the matrix is
-        # small enough for a dense SVD, and otherwise keeps this factorization (the reference's
-        # sparse LU only bails on exact singularity) under the orthogonality-driven refinement
-        self.ill_conditioned = rc == -6
-        if rc == -6:
-            rc = 0
-        if rc == -5:
-            raise BandedNotDecoupled("A A' (m=%d, half bandwidth %d): separator blocks of the "
-                                     "partitioned factorization are coupled" % (self.m, self.k))
-        _hip.check(rc, "ipx_banded_status")
-
-    POOL_MAX = 4
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if not h:
-            return
-        pool = getattr(self, "_pool", None)
-        try:
-            if pool is not None and len(pool) < self.POOL_MAX:
-                pool.append((self._key, h, self.band))       # next factorization on this pattern
-            else:
-                _hip.load().ipx_banded_destroy(ctypes.c_void_p(h))
-        except Exception:
-            pass
-
-    def _gather(self, x, idx):
-        out = dv._empty(len(x))
-        _hip.call("ipx_gather", len(x), _p(x.t), _p(idx), None, None, _p(out), stream_ptr())
-        return DVec(out)
-
-    def solve(self, w):
-        """v = (A A')^-1 w, in the caller's (unpermuted) row order."""
-        if self.perm is not None:
-            w = self._gather(w, self.perm)
-        out = dv._empty(self.m)
-        _hip.call("ipx_banded_solve", ctypes.c_void_p(self.handle), _p(w.t), _p(out), stream_ptr())
-        v = DVec(out)
-        if self.perm is not None:
-            v = self._gather(v, self.iperm)
-        return v
 
 
 class _Op:
@@ -580,7 +237,6 @@ class SVDProjector:
 
     def __init__(self, A, orth_tol, max_refin, tol):
         import scipy.linalg
-        from .dense import DeviceDense
         self.A = A
         self.m, self.n = A.shape
         if self.m * self.n > self.MAX_ELEMENTS:
@@ -650,183 +306,11 @@ def orthogonality(A, g):
     return dv.norm(A.dot(g)) / (norm_A * norm_g)
 
 
-def _box_schur_applies(A, kmax, any_sparsity=False):
-    """Pattern test: enough box-like rows, and the general rows alone are banded -- or, with
-    ``any_sparsity``, of any pattern (the Schur complement then goes to the dense or the
-    iterative solver: boxschur.BoxSchurNormalSolver)."""
-    from .boxschur import analysis_for
-    an = analysis_for(A.pattern)
-    if not an.worthwhile:
-        return False
-    if any_sparsity:
-        return len(an.general) > 0
-    return _general_rows_half_bandwidth(A) <= kmax
-
-
-def _general_rows(A):
-    """The selection of the rows the box-Schur elimination leaves to its inner solver (made
-    once per pattern, cached on it; boxschur.py reads the same attribute)."""
-    from .boxschur import analysis_for
-    from .device_mode import RowSelection
-    cache = getattr(A.pattern, "_ipx_box_general_pattern", None)
-    if cache is None:
-        an = analysis_for(A.pattern)
-        cache = A.pattern._ipx_box_general_pattern = RowSelection(A.pattern, an.general, None)
-    return cache
-
-
-class PcgArgs(ctypes.Structure):
-    """Mirror of ipx_pcg_args (include/ipx.h)."""
-    _P, _I = ctypes.c_void_p, ctypes.c_int64
-    _fields_ = [("m", _I), ("n", _I),
-                ("A_rowptr", _P), ("A_colidx", _P), ("A_val", _P), ("A_tiles", _P), ("A_ntiles", _I),
-                ("At_rowptr", _P), ("At_colidx", _P), ("At_val", _P), ("At_tiles", _P),
-                ("At_ntiles", _I), ("dinv", _P), ("v", _P), ("r", _P), ("p", _P), ("Sp", _P),
-                ("t", _P), ("state", _P), ("part1", _P), ("part2", _P), ("grid", _I),
-                ("binv", _P), ("border", _P), ("nblk", _I), ("z", _P), ("part3", _P)]
-
-
-class IterativeNormalSolver:
-    """``(A A')^-1`` without a factorization, for sparse Jacobians whose ``A A'`` is neither
-    banded (after reordering) nor small enough for the dense device Cholesky: preconditioned
-    conjugate gradients on ``A (A' v) = w``, device resident (csrc/pcg.hip):
-    one C call enqueues a batch of iterations, convergence and stall tests are taken on the
-    device, the host reads one state block per batch.  The reference factors any sparse A
-    with SuperLU (projections.py:93-172); this keeps such problems solvable here (at the
-    speed of an iterative solve) instead of refusing them.  The inner solve runs to the
-    floor of fp64; the projector's orthogonality-driven refinement (projections.py:72-78)
-    sits on top of it as usual.
-
-    Preconditioner (``precond``): "block" (default) -- block Jacobi: the diagonal 32 x 32 blocks
-    of ``A A'`` with the rows taken in the bandwidth-reducing order of the symbolic analysis
-    (reverse Cuthill-McKee of the pattern of ``A A'``), formed, Cholesky-factored and inverted
-    on the device once per factorization; "jacobi" -- the diagonal (round 2)."""
-
-    perm = None
-    RTOL, MAXIT = 1e-15, 2000
-    WARN_RELRES = 1e-10          # a solve that ends above this says so (warning)
-    PS_RZ0, PS_BEST0, PS_DONE, PS_ITERS, PS_NORM_W, PS_RTOL, PS_STALL_FAR = 0, 2, 6, 7, 8, 9, 11
-    STALL_FAR = 30               # iterations without a new smallest residual that end a solve
-                                 # whose residual is still above 1e-9 ||w|| (5 below that)
-    BLOCK = 32
-
-    def __init__(self, A, precond="block"):
-        lib = _hip.load()
-        self.precond = precond
-        self.A, self.At = A, A.T
-        self.m, n = A.shape
-        sq = DVec(A.val) * DVec(A.val)
-        rowsq = DeviceCSR(A.pattern, sq.t).dot(DVec.full(n, 1.0))
-        d = rowsq.to_host()
-        if not np.all(d > 0):
-            raise np.linalg.LinAlgError("Singular Jacobian matrix: a row of A is zero")
-        self.dinv = DVec.from_host(1.0 / d)
-        dev, m = ctx().device, self.m
-        z = lambda k: torch.zeros(int(k), dtype=_F64, device=dev)
-        self.r, self.p, self.Sp, self.t = z(m), z(m), z(m), z(n)
-        self.state = z(lib.ipx_pcg_state_size())
-        self.grid = int(lib.ipx_cg_vec_grid(max(m, 1)))
-        self.part1, self.part2 = z(2 * A.pattern.ntiles), z(2 * self.grid)
-        a = self.args = PcgArgs()
-        a.m, a.n = m, n
-        for pre, M in (("A", A), ("At", self.At)):
-            pat = M.pattern
-            setattr(a, pre + "_rowptr", pat.indptr.data_ptr())
-            setattr(a, pre + "_colidx", pat.indices.data_ptr())
-            setattr(a, pre + "_val", M.val.data_ptr())
-            setattr(a, pre + "_tiles", pat.tiles.data_ptr())
-            setattr(a, pre + "_ntiles", pat.ntiles)
-        a.dinv = self.dinv.t.data_ptr()
-        a.r, a.p, a.Sp, a.t = (t.data_ptr() for t in (self.r, self.p, self.Sp, self.t))
-        a.state, a.part1, a.part2 = (t.data_ptr() for t in (self.state, self.part1, self.part2))
-        a.grid = self.grid
-        if precond == "block":
-            # rows in the order of the symbolic analysis, padded to whole blocks
-            order = _symbolic_for(A.pattern).perm
-            order = np.arange(m, dtype=np.int32) if order is None else np.asarray(order, np.int32)
-            nblk = (m + self.BLOCK - 1) // self.BLOCK
-            padded = np.full(nblk * self.BLOCK, -1, dtype=np.int32)
-            padded[:m] = order
-            self.border = torch.from_numpy(padded).to(dev)
-            self.binv = torch.empty(nblk * self.BLOCK * self.BLOCK, dtype=_F64, device=dev)
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            pat = A.pattern
-            _hip.call("ipx_blockjacobi_build", nblk, _p(pat.indptr), _p(pat.indices), _p(A.val),
-                      _p(self.border), _p(self.binv), _p(flag), stream_ptr())
-            fl = int(flag.item())
-            if fl & 1:
-                raise np.linalg.LinAlgError("Singular Jacobian matrix: a diagonal block of A A' "
-                                            "is not positive definite")
-            # bit 2 alone: every pivot positive, one lost 43 bits (a block numerically rank
-            # deficient); the solve goes on, as with the dense factorization
-            self.ill_conditioned = bool(fl & 2)
-            self.z, self.part3 = z(m), z(nblk // 8 + 2)
-            self.dinv = DVec.zeros(m)             # (r'z comes from the block kernel)
-            a.dinv = self.dinv.t.data_ptr()
-            a.binv, a.border, a.nblk = self.binv.data_ptr(), self.border.data_ptr(), nblk
-            a.z, a.part3 = self.z.data_ptr(), self.part3.data_ptr()
-        elif precond != "jacobi":
-            raise ValueError("precond must be 'block' or 'jacobi'")
-        self.stats = {"solves": 0, "iterations": 0, "batches": 0}
-
-    def solve(self, w):
-        lib = _hip.load()
-        v = DVec.zeros(self.m)
-        norm_w = dv.norm(w)
-        if norm_w == 0:
-            return v
-        self.r.copy_(w.t)
-        init = np.zeros(self.state.numel())
-        if self.precond == "block":
-            self.state.zero_()
-            _hip.call("ipx_blockjacobi_apply", self.m, self.args.nblk, _p(self.border),
-                      _p(self.binv), _p(w.t), _p(self.z), _p(self.part3), _p(self.state),
-                      stream_ptr())
-            z0 = DVec(self.z)
-        else:
-            z0 = self.dinv * w
-        self.p.copy_(z0.t)
-        init[self.PS_RZ0] = w.dot(z0)
-        init[self.PS_BEST0] = np.inf
-        init[self.PS_NORM_W], init[self.PS_RTOL] = norm_w, self.RTOL
-        init[self.PS_STALL_FAR] = self.STALL_FAR
-        self.state.copy_(torch.from_numpy(init))
-        self.args.v = v.t.data_ptr()
-        it, batch = 0, 8
-        while it < self.MAXIT:
-            end = min(self.MAXIT, it + batch)
-            _hip.check(lib.ipx_pcg_iterate(ctypes.byref(self.args), it, end, stream_ptr()),
-                       "ipx_pcg_iterate")
-            s = self.state.tolist()               # one blocking read per batch
-            self.stats["batches"] += 1
-            if s[self.PS_DONE] != 0:
-                if s[self.PS_DONE] == 3:
-                    raise np.linalg.LinAlgError("Singular Jacobian matrix: A A' is not positive "
-                                                "definite")
-                break
-            it, batch = end, min(2 * batch, 64)
-        self.stats["solves"] += 1
-        self.stats["iterations"] += int(s[self.PS_ITERS])
-        # neither converged nor down at the floor of fp64 (MAXIT reached, or no progress far
-        # above it): the reference's direct factorization would have been accurate here --
-        # say so instead of returning a poor solve silently
-        relres = min(s[self.PS_BEST0], s[self.PS_BEST0 + 1]) / norm_w
-        self.stats["worst_relres"] = max(self.stats.get("worst_relres", 0.0), relres)
-        if s[self.PS_DONE] != 1 and relres > self.WARN_RELRES:
-            from warnings import warn
-            warn("IterativeNormalSolver: the preconditioned CG on A A' stopped at a relative "
-                 "residual of %.1e after %d iterations (ill-conditioned Jacobian; m = %d): "
-                 "projections with this factorization are only that accurate"
-                 % (relres, int(s[self.PS_ITERS]), self.m))
-        return v
-
-
 def as_device_matrix(A):
     """Upload a scipy sparse matrix / ndarray (device matrices pass through).
     An empty matrix is forced to the sparse representation like the
     reference does (projections.py:368-369)."""
     import scipy.sparse as sps
-    from .dense import DeviceDense
     if isinstance(A, DeviceCSR):
         return A.with_sorted_indices()
     if isinstance(A, DeviceDense):
@@ -837,154 +321,8 @@ def as_device_matrix(A):
     return DeviceDense.from_host(np.asarray(A, dtype=float))
 
 
-def _general_rows_half_bandwidth(A):
-    """Half bandwidth (after reordering) of ``A_R A_R'``, A_R the rows the box-Schur elimination
-    leaves to its inner solver."""
-    return _symbolic_for(_general_rows(A).pattern).k
-
-
-def wide_band_inner(B):
-    """The box-Schur elimination's inner solver for ``B B'`` of any sparsity under the policy
-    in force: the block-tridiagonal solver when the policy asks for it and the half bandwidth
-    allows it, else None (the caller's dense / iterative choice).  With border columns allowed
-    (``border_columns``) the bordered solver comes first, and with link rows allowed
-    (``link_rows``) the linked solver before it."""
-    solver = link_solver(B)
-    if solver is not None:
-        return solver
-    solver = bordered_solver(B)
-    if solver is not None:
-        return solver
-    if wide_band_policy() == "iterative":
-        return None
-    from .blocktri import BlockTridiagonalNormalSolver
-    k = _symbolic_for(B.pattern).k
-    if k <= _hip.load().ipx_blocktri_kmax():
-        return BlockTridiagonalNormalSolver(B)      # (also what the banded kernels would take)
-    return direct_solver_class(k)(B) if k <= border_reach() else None
-
-
-def normal_solver_for(A, deferred=None):
-    """The ``(A A')^-1`` solver ``projections`` picks for a full-row-rank device matrix."""
-    solver = _pick_normal_solver(A, deferred)
-    _last_solver[0] = solver_name(solver)
-    return solver
-
-
-def _pick_normal_solver(A, deferred=None):
-    from .dense import DenseNormalSolver, DeviceDense
-    if isinstance(A, DeviceDense):
-        return DenseNormalSolver(A)
-    kmax = _hip.load().ipx_banded_kmax()
-    m = A.shape[0]
-    if link_rows_limit() > 0:
-        # a band plus a few dense rows (linked.py), before everything else; a refusal in either
-        # place goes on with the order below
-        solver = link_solver(A)                                            # (L1)
-        if solver is not None:
-            return solver
-        if _box_schur_applies(A, kmax, any_sparsity=True) \
-                and _link_split_for(_general_rows(A).pattern) is not None:
-            # (L2) bound rows eliminated in closed form; the general rows are such a matrix (a
-            # linking inequality of a barrier problem with a box)
-            from .boxschur import BoxSchurNormalSolver
-            from .linked import LinkedRowsNormalSolver
-            solver = BoxSchurNormalSolver(A, any_sparsity=True)
-            if isinstance(solver.inner, LinkedRowsNormalSolver):
-                return solver
-    if border_columns_limit() > 0:
-        # a band plus a few dense columns (bordered.py), before everything else; a refusal in
-        # either place goes on with the order below
-        solver = bordered_solver(A)                                        # (D1)
-        if solver is not None:
-            return solver
-        if _box_schur_applies(A, kmax, any_sparsity=True) \
-                and _border_split_for(_general_rows(A).pattern) is not None:
-            # (D2) bound rows eliminated in closed form; the general rows are such a matrix
-            from .bordered import BorderedNormalSolver
-            from .boxschur import BoxSchurNormalSolver
-            solver = BoxSchurNormalSolver(A, any_sparsity=True)
-            if isinstance(solver.inner, BorderedNormalSolver):
-                return solver
-    # the wide-band policy (see ``wide_band``): dense A and half bandwidths <= kmax keep their
-    # order; three places differ, marked (W1)-(W3)
-    wide = wide_band_policy() != "iterative"
-    if wide:
-        from .blocktri import BlockTridiagonalNormalSolver
-        bt_kmax = border_reach()        # (64, or 256 under "block-tridiagonal-wide")
-    if half_bandwidth_of_aat(A.pattern) > kmax and _box_schur_applies(A, kmax):
-        # the barrier problem's augmented Jacobian: a general row couples with the two bound
-        # rows of each of its variables, no reordering of A A' is narrow -- skip the attempt
-        from .boxschur import BoxSchurNormalSolver
-        try:
-            return BoxSchurNormalSolver(A)
-        except BandedNotDecoupled:
-            if wide:                            # (W1) the Schur complement is such a band
-                return BoxSchurNormalSolver(A, any_sparsity=True)
-    if wide and _box_schur_applies(A, kmax, any_sparsity=True) \
-            and kmax < _general_rows_half_bandwidth(A) <= bt_kmax:
-        # (W2) bound rows eliminated in closed form, the general rows' Schur complement
-        # J (I - W) J' + S^2 (the pattern of A_R A_R') factored directly, for any m
-        from .boxschur import BoxSchurNormalSolver
-        return BoxSchurNormalSolver(A, any_sparsity=True)
-    k = _symbolic_for(A.pattern).k
-    if k <= kmax:
-        try:
-            return BandedNormalSolver(A, deferred=deferred)
-        except BandedNotDecoupled:
-            # Half bandwidths 5-8 on a long band run the single-launch decoupled solve (the
-            # separator system, half bandwidth 2k-1, is only formed to test that its blocks
-            # decouple).  When they do not, a serial sweep would take 80-100 ms per solve at
-            # m = 1e5: the device-resident preconditioned CG is 20x faster and as accurate
-            # after the projector's refinement (profiles/r02_banded_by_bandwidth.txt).
-            if wide:
-                return BlockTridiagonalNormalSolver(A)      # (W1) blocks of 16, any m
-            if m > DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
-                return IterativeNormalSolver(A)
-    if _box_schur_applies(A, kmax):
-        from .boxschur import BoxSchurNormalSolver
-        try:
-            return BoxSchurNormalSolver(A)      # bound rows eliminated analytically
-        except BandedNotDecoupled:
-            # the Schur complement of the general rows is such a coupled wide band: the
-            # elimination buys nothing, solve with A itself by the paths below
-            if wide:
-                return BoxSchurNormalSolver(A, any_sparsity=True)          # (W1)
-    if wide and kmax < k <= bt_kmax:
-        return direct_solver_class(k)(A)        # (W3) block cyclic reduction, any m
-    if m <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
-        return DenseNormalSolver(A)             # wide band: dense Cholesky of A A'
-    if _box_schur_applies(A, kmax, any_sparsity=True):
-        # barrier problem with a Jacobian of general sparsity (the reference factors any
-        # pattern with SuperLU, projections.py:93-172): the bound rows -- two thirds of the
-        # matrix, and the ones whose slacks ruin the conditioning of A A' late in the barrier
-        # run -- are still eliminated in closed form; what is left to the dense / iterative
-        # solver is the Schur complement of the general rows, J (I - W) J' + S^2
-        from .boxschur import BoxSchurNormalSolver
-        return BoxSchurNormalSolver(A, any_sparsity=True)
-    return IterativeNormalSolver(A)             # general sparsity: matrix-free solve
-
-
-def _banded_row_order(A):
-    """The row order in which A A' is banded when the natural one is not and the banded solver
-    would be the choice of ``normal_solver_for`` (not the box-Schur elimination, which has its
-    own row bookkeeping); None otherwise."""
-    kmax = _hip.load().ipx_banded_kmax()
-    if half_bandwidth_of_aat(A.pattern) <= kmax:
-        return None
-    if _box_schur_applies(A, kmax):
-        return None
-    if _border_split_for(A.pattern) is not None:
-        return None             # (the bordered solver's band has its own order; A A' is full)
-    if _link_split_for(A.pattern) is not None:
-        return None             # (likewise the linked solver's)
-    sym = _symbolic_for(A.pattern)
-    return sym.perm if (sym.k <= kmax and sym.perm is not None) else None
-
-
 def _rows_in_order(A, perm):
     """``A[perm]`` as a value refresh on a pattern derived once from A's (cached on it)."""
-    from .device_mode import RowSelection
     sel = getattr(A.pattern, "_ipx_rows_in_order", None)
     if sel is None:
         sel = A.pattern._ipx_rows_in_order = RowSelection(A.pattern, np.asarray(perm, dtype=np.int64), None)
@@ -998,7 +336,6 @@ def projections(A, method=None, orth_tol=1e-12, max_refin=3, tol=1e-15, deferred
     ``method`` accepts the reference's names; every one maps to the device
     normal-equation solve (the operators are the same; see module docstring).
     """
-    from .dense import DenseNormalSolver
     A = as_device_matrix(A)
     # The SAME matrix object with unchanged values: the factorization made for it is returned.
     # Values declared immutable (``constant``: linear constraints, N1) are factored once per
@@ -1014,8 +351,7 @@ def projections(A, method=None, orth_tol=1e-12, max_refin=3, tol=1e-15, deferred
     # reference to the tensor it was made for: a reassigned ``A.val`` can then never collide
     # with a collected tensor's id.
     t, version = _values_version(A)
-    key = (method, orth_tol, max_refin, tol, version, wide_band_policy(), border_columns_limit(),
-           link_rows_limit())
+    key = (method, orth_tol, max_refin, tol, version, solver_options.current().key())
     cached = getattr(A, "_ipx_projections", None)
     if cached is not None and version is not None and cached[0] == key and cached[2] is t:
         # (a caller that cannot take a pending verdict along gets it settled first)
@@ -1065,7 +401,6 @@ def _values_version(A):
 
 
 def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
-    from .dense import DenseNormalSolver
     sparse = isinstance(A, DeviceCSR)
     if sparse:
         if method not in (None, "NormalEquation", "AugmentedSystem"):
@@ -1105,8 +440,3 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
     return NormalEquationProjector(A, solver, orth_tol, max_refin, row_perm=row_perm,
                                    lazy_norm=deferred is not None).operators()
 
-
-from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: E402,F401  (public here)
-from .blockwide import WideBlockTridiagonalNormalSolver  # noqa: E402,F401  (public here)
-from .bordered import BorderedNormalSolver, BorderedRefused, border_split  # noqa: E402,F401
-from .linked import LinkedRowsNormalSolver, LinkedRefused, link_split  # noqa: E402,F401

@@ -1,0 +1,92 @@
+"""The scoped options of the ``(A A')^-1`` solver selection (selection.py), in one record.
+
+``wide_band``: what takes a sparse A whose ``A A'`` is banded past the banded kernels' half
+bandwidth -- "iterative" (default): the dense Cholesky while it fits, else the preconditioned CG;
+"block-tridiagonal": block cyclic reduction (blocktri.py) up to half bandwidth 64;
+"block-tridiagonal-wide": the same, and blocks of 128 / 256 (blockwide.py) for half bandwidths
+65 ... 256.
+
+``border_columns``: up to this many columns of a sparse A may be split off as a border when the
+rest is banded / block tridiagonal in ``A A'`` (bordered.py).  ``link_rows``: likewise up to this
+many rows (linked.py).  0, the default of both: off, every path as without the option.
+
+Scoped: ``with scoped(wide_band="block-tridiagonal", link_rows=4): ...`` holds any subset for the
+duration of the block.  ``current().key()`` is part of the key of every cached factorization: a
+new option is a new field here and nowhere else.
+"""
+import collections
+import contextlib
+
+import numpy as np
+
+from . import _hip
+
+WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide")
+
+
+class Options(collections.namedtuple("Options", "wide_band border_columns link_rows")):
+    __slots__ = ()
+
+    def key(self):
+        """What tells two settings apart in a cache key."""
+        return tuple(self)
+
+
+_current = [Options("iterative", 0, 0)]
+
+
+def current():
+    return _current[0]
+
+
+def check(name, value):
+    """``value`` as option ``name`` holds it, or ValueError."""
+    if name == "wide_band":
+        if value not in WIDE_BAND_POLICIES:
+            raise ValueError("wide_band must be one of %s, not %r"
+                             % (", ".join(repr(p) for p in WIDE_BAND_POLICIES), value))
+        return value
+    if name not in Options._fields:
+        raise ValueError("unknown solver option %r" % (name,))
+    most = _hip.load().ipx_border_pmax()
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) \
+            or not 0 <= value <= most:
+        raise ValueError("%s must be an integer in 0 ... %d, not %r" % (name, most, value))
+    return int(value)
+
+
+@contextlib.contextmanager
+def scoped(**changes):
+    """Hold the given options for the duration of the block (restored on any exit)."""
+    previous = _current[0]
+    _current[0] = previous._replace(**{name: check(name, v) for name, v in changes.items()})
+    try:
+        yield
+    finally:
+        _current[0] = previous
+
+
+def pop_from(options):
+    """The solver options of a user's ``options`` dict, checked and taken out of it (an option
+    that is not given: the value in force), as the keywords of ``scoped``."""
+    return {name: check(name, options.pop(name, getattr(current(), name)))
+            for name in Options._fields}
+
+
+def _wrappers(name):
+    def hold(value):
+        return scoped(**{name: value})
+
+    def get():
+        return getattr(current(), name)
+
+    def check_one(value):
+        return check(name, value)
+    hold.__doc__ = "Hold ``%s`` for the duration of the block (restored on any exit)." % name
+    return hold, get, check_one
+
+
+# the names callers have used since each option was added
+wide_band, wide_band_policy, check_wide_band = _wrappers("wide_band")
+border_columns, border_columns_limit, check_border_columns = _wrappers("border_columns")
+link_rows, link_rows_limit, check_link_rows = _wrappers("link_rows")

@@ -31,6 +31,7 @@ import time
 
 import numpy as np
 
+from . import solver_options
 from . import sqp_chain as sc
 from .sqp_chain import (RADIUS, PENALTY, F, NORM_B, NORM_DN, RADIUS_T, HDD, CD, LIN, NORM_D,
                         NORM_DT, PRED, MERIT, F_NEXT, NORM_B_NEXT, RATIO, SOC, ACCEPT,
@@ -418,10 +419,8 @@ def _settle_key(pt, method):
     tens = (getattr(pt.A, "val", None), getattr(pt.c, "t", None), getattr(pt.b, "t", None))
     if any(t is None or not hasattr(t, "_version") for t in tens):
         return None
-    # (a factorization belongs to its policy, its border-column limit and its link-row limit)
-    from .projector import wide_band_policy, border_columns_limit, link_rows_limit
-    return ((method, wide_band_policy(), border_columns_limit(), link_rows_limit()),) \
-        + tuple((t, t._version) for t in tens)
+    # (a factorization belongs to the solver options it was made under)
+    return ((method,) + solver_options.current().key(),) + tuple((t, t._version) for t in tens)
 
 
 def _same_key(a, b):
