@@ -265,7 +265,8 @@ int ipx_aat_band(int64_t m, int32_t k, const int32_t *rowptr, const int32_t *col
                  const double *val, const int32_t *perm, double *band, void *stream);
 
 /* ---- device-resident projected CG (qp_subproblem.py:549-634): see csrc/cg.hip.
- * The argument block holds device pointers only; every member is 8 bytes. */
+ * The argument block holds device pointers only; every member is 8 bytes (but the last one,
+ * an int32 flag). */
 typedef struct ipx_cg_args {
   int64_t n, m;
   const int32_t *A_rowptr, *A_colidx; const double *A_val; const int32_t *A_tiles; int64_t A_ntiles;
@@ -376,7 +377,43 @@ typedef struct ipx_cg_args {
   double *LR_part;
   int64_t LR_mem;
   int64_t LR_rows;
+  /* Carried sums for the radius test of qp_subproblem.py:583 (both fused kernels in use, no
+   * box, finite radius; NULL: the test reads x and p as before).  k_cg_step2_hp of iteration
+   * `it` has x_next and p_next on its own rows in registers and leaves per row tile of H the
+   * partials of sum x^2, sum x p, sum p^2, and the tag it + 1 ("these sums belong to the x and
+   * p iteration it + 1 starts from").  The fused step1 + A.r kernel of iteration it + 1 then
+   * reads neither x nor p: its first ceil(H_ntiles / 64) workgroups fold one 64-entry slice of
+   * the three arrays each (NaNs when the tag is not `it`), and that
+   * iteration's k_cg_step2_hp forms ||x + alpha p||^2 = XX + 2 alpha XP + alpha^2 PP from the
+   * folded sums.  It decides :583 only when the sums are this iteration's and the value lies
+   * outside a relative band of 1e-9 around radius^2 (IPX_CG_STOP_RADIUS_UNDECIDED otherwise:
+   * the host forms the norm).
+   * Layout, doubles: [0, 3 H_ntiles) the partials, array by array; [3 H_ntiles] their tag;
+   * then three arrays of 256 for the folded sums (ceil(H_ntiles / 64) <= 256 entries used, the
+   * rest stays zero) and one spare double: 3 H_ntiles + 770 in all, zeroed once.  More than
+   * 16384 row tiles of H (n beyond ~1.1e7 at 3 entries per row): the test reads x and p.
+   * Every entry point that changes x or p
+   * outside k_cg_step2_hp clears the tag (ipx_cg_hp, ipx_cg_prime, ipx_cg_resume,
+   * ipx_cg_save_pb, the resident launch, an ipx_cg_iterate batch with no_radius set).  The
+   * stand-alone ipx_cg_step2_hp runs the kernel without the sums and leaves the tag alone: do
+   * not set xsums_carry behind it. */
+  double *xsums;
+  /* != 0: the first iteration of the next ipx_cg_iterate call may take the carried sums too
+   * -- the caller knows that the previous batch on this block ended exactly there without a
+   * stop and that nothing has run on it since.  0: that iteration reads x and p. */
+  int32_t xsums_carry;
 } ipx_cg_args;
+/* k_cg_step2_hp mode bits: 1 = no radius / box test, 2 = no orthogonality test (the two
+ * ipx_cg_resume and ipx_cg_step2_hp take), 4 = the radius test from the carried sums (set by
+ * ipx_cg_iterate alone). */
+#define IPX_CG_MODE_NO_RADIUS 1
+#define IPX_CG_MODE_NO_ORTH 2
+#define IPX_CG_MODE_CARRIED 4
+/* Stop code 10 of the state block: the carried sums could not decide the radius test (inside
+ * the band, or their tag is not this iteration's).  Nothing of the iteration's step2 was
+ * committed; the host forms ||x + alpha p|| itself and takes the exit of :583 or resumes
+ * (ipx_cg_resume, mode 1). */
+#define IPX_CG_STOP_RADIUS_UNDECIDED 10
 int ipx_cg_resident_ok(const ipx_cg_args *a);
 int64_t ipx_cg_resident_ll_words(int32_t nwg, int32_t hw);
 /* the kernel's budgets for the host code that builds its tables: workgroups per launch, threads,

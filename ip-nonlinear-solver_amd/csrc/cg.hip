@@ -436,6 +436,27 @@ k_cg_step2(int64_t n, double *st, int parity, int mode, const double *__restrict
 // (halo <= 64 and <= the shortest tile: checked by the host binding, cg_fused.fuse_halo)
 constexpr int FT_NNZ = IPX_SPMV_TILE_NNZ;
 
+// Carried sums for the radius test (ipx_cg_args.xsums; BOX = false, PEER = false only): what
+// k_cg_step2_hp of iteration `it` writes and, with mode bit 4, reads.
+//   raw  != NULL: the block's base.  write: the tile's partials of sum x_next^2, x_next p_next,
+//        p_next^2 go to raw[q * ntiles + tile] and the lead lane tags them it + 1; !write: x
+//        and p change without them, the lead lane clears the tag.
+//   in (mode bit 4): the folded sums from the fused step1 + A.r kernel of this iteration, three
+//        arrays XS_STRIDE apart (zeros behind their <= XS_STRIDE entries) -- lane t of the
+//        workgroup takes entry t of each with the three loads it would spend on the
+//        ||x + alpha p||^2 partials, in the same straight-line prologue (a branch there splits
+//        the block the fold's loads and the tile's loads are scheduled in: measured +1.5 us).
+//        That kernel has compared the raw partials' tag with `it` and left NaNs where they
+//        are not this iteration's.
+struct ipx_xsums_job {
+  double *raw;
+  const double *in;
+  int it, write;
+};
+constexpr int XS_SLICE = 64;     // raw partials per folded sum (one wave of k_cg_step1_ar)
+constexpr int XS_STRIDE = IPX_BLOCK;   // distance of the three arrays of folded sums
+constexpr double XS_BAND = 1e-9; // the carried form decides :583 only outside this relative band
+
 // C16: the column indices come as 16-bit offsets into the tile's span (col - c_lo, built once
 // per pattern by the host binding) and the row pointers of a tile whose rows all have the
 // same length are not read at all (rowlen[tile] >= 0): 2 + 4/rowlen bytes less per nonzero of
@@ -448,7 +469,10 @@ constexpr int FT_NNZ = IPX_SPMV_TILE_NNZ;
 // entries into the neighbours' mailboxes, the tiles whose span reaches into the rank's halo
 // take those entries from the mailbox (and write them into g, whose halo the next iteration's
 // step1 reads).
-template <bool HAS_DIAG, int Q, int QS, bool BOX, bool C16, bool PEER>
+// XSUM: the instantiation that writes and / or consumes the carried sums of the radius test
+// (ipx_xsums_job).  The launcher picks it only for launches that do; every other launch -- the
+// trust_radius = inf loop, the stand-alone entry, BOX, PEER -- runs the kernel without them.
+template <bool HAS_DIAG, int Q, int QS, bool BOX, bool C16, bool PEER, bool XSUM = false>
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict__ p2, int np2,
               const double *__restrict__ p3, int np3, const double *__restrict__ p4, int np4,
@@ -459,11 +483,15 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
               double *__restrict__ partial, int hmax, const double *__restrict__ pb_in,
               double *__restrict__ pb_out,
               const uint16_t *__restrict__ col16, const int32_t *__restrict__ rowlen,
-              typename peer_arg<PEER>::type pj, double *g_halo) {
+              typename peer_arg<PEER>::type pj, double *g_halo, ipx_xsums_job xs) {
+  constexpr bool XS = XSUM;                    // the carried sums of the radius test
+  static_assert(!XSUM || (!BOX && !PEER), "carried sums: no box, one GPU");
+  // (the folded sums ride in the three loads per lane of the xn2 partials: ipx_fold_regs<2, 3>)
+  static_assert(XS_STRIDE == IPX_BLOCK, "one folded entry per lane and load");
   __shared__ double prod[FT_NNZ];
   __shared__ double span[QS * IPX_BLOCK];
   __shared__ int rp[Q * IPX_BLOCK + 1];
-  __shared__ double lds[4 * (IPX_BLOCK / IPX_WAVE)];
+  __shared__ double lds[(XSUM ? 5 : 4) * (IPX_BLOCK / IPX_WAVE)];
   __shared__ double plds[PEER ? 4 * IPX_MAX_PEERS + 1 : 1];
   CG_STAMP(0);
   const int tile = ipx_xcd_item(blockIdx.x, ntiles);
@@ -476,8 +504,11 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   // BOX = false (no bounds): the violation counts are all zero and are not read; the
   // ||x + alpha p||^2 partials -- one per row tile of A when step1 is fused -- get the
   // freed register instead
-  const double *const partsA[2] = {BOX ? p2 + np2 : p2, p4};
-  const int countsA[2] = {(mode & 1) ? 0 : np2, (mode & 2) ? 0 : np4};
+  // (mode bit 4: the folded carried sums take the place of the ||x + alpha p||^2 partials --
+  // load u of this lane is its entry of array u)
+  const bool carried = XS && (mode & 4) != 0;
+  const double *const partsA[2] = {BOX ? p2 + np2 : (carried ? xs.in : p2), p4};
+  const int countsA[2] = {(mode & 1) ? 0 : (carried ? 3 * XS_STRIDE : np2), (mode & 2) ? 0 : np4};
   const double *const partsB[1] = {p3};
   const int countsB[1] = {np3};
   const double *const partsC[1] = {BOX ? p2 : p2 + np2};     // BOX: xn2;  else unused (count 0)
@@ -533,7 +564,7 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   if (PEER && stop == 7.0) return;
   CG_STAMP(1);
   const bool lead = tile == 0 && tid == 0;
-  double red[4], loc[4];
+  double red[5], loc[5];
   {
     double la[2], lb1[1], lc[1] = {0.0};
     foldA.local(partsA, countsA, la);
@@ -543,8 +574,23 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     loc[1] = BOX ? la[0] : 0.0;                    // viol      xn2, viol, gg, tt)
     loc[2] = lb1[0];                               // gg
     loc[3] = la[1];                                // tt
+    // carried: XX in xn2's place, XP in the (no box: unused) violation count's, PP behind
+    // them (selects, one barrier pair as before)
+    if constexpr (XS) {
+      loc[0] = carried ? foldA.t[0][0] : loc[0];
+      loc[1] = carried ? foldA.t[0][1] : loc[1];
+      loc[4] = carried ? foldA.t[0][2] : 0.0;
+    }
   }
-  ipx_block_sum_multi<4>(loc, lds, red);
+  if constexpr (XS) {
+    ipx_block_sum_multi<5>(loc, lds, red);
+  } else {
+    double l4[4] = {loc[0], loc[1], loc[2], loc[3]}, r4[4];
+    ipx_block_sum_multi<4>(l4, lds, r4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[q] = r4[q];
+    red[4] = 0.0;
+  }
   if constexpr (PEER) {
     const ipx_peer_view &pv = pj.pv;
     const int par = pj.hseq & 1;
@@ -563,8 +609,8 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
         for (int j = tid; j < pj.send_right[k]; j += IPX_BLOCK)
           ipx_ll_store(pv.mbox[pv.rank + 1] + ipx_peer_halo_word(pv.cap, 0, par, pj.push_r[k] + j),
                        g[pj.own_hi[k] - pj.send_right[k] + j], pj.hseq);
-    double tot[4];
-    bool ok = ipx_peer_sum<4>(pv, pj.seq, 0, red, tile == 0, plds, tot);
+    double tot[4], red4[4] = {red[0], red[1], red[2], red[3]};
+    bool ok = ipx_peer_sum<4>(pv, pj.seq, 0, red4, tile == 0, plds, tot);
 #pragma unroll
     for (int q = 0; q < 4; ++q) red[q] = tot[q];
     // (where the launch-per-collective form leaves them: the host's event handlers and the
@@ -601,7 +647,23 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     if (stop != 0.0) return;
   }
   if (!(mode & 1)) {
-    const double xn2 = red[0], viol = red[1];
+    double xn2 = red[0], viol = red[1];
+    if (carried) {
+      // ||x + alpha p||^2 from the sums over the x and p this iteration started from.  M bounds
+      // the terms that went into it, so the band covers their cancellation too.  Inside the
+      // band, or with sums that are not this iteration's (NaNs: k_cg_step1_ar), the host forms
+      // the norm (stop code 10, nothing committed).  radius^2 = +inf (radius 1e300, inf) lies
+      // outside the band of every finite M; a non-finite M or value decides nothing.
+      const double XX = red[0], XP = red[1], PP = red[4];
+      const double a2 = alpha * alpha, r2 = radius * radius;
+      xn2 = (XX + 2.0 * (alpha * XP)) + a2 * PP;
+      const double M = (XX + 2.0 * fabs(alpha * XP)) + a2 * PP;
+      if (!(fabs(xn2 - r2) > XS_BAND * M)) {
+        if (lead) st[ST_STOP] = (double)IPX_CG_STOP_RADIUS_UNDECIDED;
+        return;
+      }
+      viol = 0.0;
+    }
     if (sqrt(xn2) >= radius) {                       // :583
       if (lead) { st[ST_XNORM2] = xn2; st[ST_STOP] = 2.0; }
       return;
@@ -625,6 +687,8 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     st[parity ? ST_RTG0 : ST_RTG1] = gg;             // :633
     st[ST_BETA] = beta;
     st[ST_IT_DONE] += 1.0;
+    // x and p change below: tag the sums this launch leaves, or void those it does not renew
+    if constexpr (XS) xs.raw[3 * ntiles] = xs.write ? (double)(xs.it + 1) : 0.0;
   }
   // p_next on the span (LDS), x_next / p_next / boundary copies on the own rows
   double *pbo = pb_out + (int64_t)tile * 2 * hmax;
@@ -694,7 +758,40 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     }
   }
   CG_STAMP(6);
-  {
+  const bool xs_out = XS && xs.write != 0;
+  double acc_xx = 0.0, acc_xp = 0.0, acc_pp = 0.0;
+  // x_next on own span element k of this lane (x was requested before the SpMV phases and has
+  // landed); false: not an own row
+  auto x_next = [&](int k, double &xn) {
+    const int col = c_lo + tid + k * IPX_BLOCK;
+    xn = sx[k] + alpha * sp[k];                      // :580,630
+    return col >= r0 && col < r1;
+  };
+  // the sums the next iteration's radius test is formed from: x_next = x + alpha p on the own
+  // rows (x was requested before the SpMV phases and has landed) and p_next (still in the span)
+  if (xs_out) {
+#pragma unroll
+    for (int k = 0; k < QS; ++k) {
+      double xn;
+      if (x_next(k, xn)) {
+        const double pn = span[tid + k * IPX_BLOCK];
+        acc_xx += xn * xn;
+        acc_xp += xn * pn;
+        acc_pp += pn * pn;
+      }
+    }
+  }
+  if (xs_out) {
+    double red5[5] = {acc_yy, acc_xy, acc_xx, acc_xp, acc_pp}, out5[5];
+    ipx_block_sum_multi<5>(red5, lds, out5);
+    if (tid == 0) {
+      partial[tile] = out5[0];
+      partial[ntiles + tile] = out5[1];
+      xs.raw[tile] = out5[2];
+      xs.raw[ntiles + tile] = out5[3];
+      xs.raw[2 * ntiles + tile] = out5[4];
+    }
+  } else {
     double red2[2] = {acc_yy, acc_xy}, out2[2];
     ipx_block_sum_multi<2>(red2, lds, out2);
     // (PEER: the tiles of halo rows leave zeros, so that the consumer may fold the whole array
@@ -711,12 +808,10 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     const int i = tid + q * IPX_BLOCK;
     if (i < nrows) Hp[r0 + i] = yq[q];
   }
-  // x_next = x + alpha p on the own rows (x was requested before the SpMV phases and has
-  // landed)
 #pragma unroll
   for (int k = 0; k < QS; ++k) {
-    const int col = c_lo + tid + k * IPX_BLOCK;
-    if (col >= r0 && col < r1) x[col] = sx[k] + alpha * sp[k];       // :580,630
+    double xn;
+    if (x_next(k, xn)) x[c_lo + tid + k * IPX_BLOCK] = xn;
   }
   CG_STAMP(7);
 }
@@ -733,14 +828,20 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
 // r, so outside the iteration nothing changes.  Same expressions in the same
 // order as k_cg_step1 + k_csr_spmv; the ||x + alpha p||^2 partials are per tile
 // instead of per vector chunk (same values up to the order of summation).
-// NOXN2: trust radius +inf -- ||x + alpha p||^2 can only feed a comparison that is always false
-// (:583) and is not formed: x and p are not read at all (16 of the 56 MB this kernel moves at
-// n = 1e6).
+// XN = 1 (NOXN2): trust radius +inf -- ||x + alpha p||^2 can only feed a comparison that is
+// always false (:583) and is not formed: x and p are not read at all (16 of the 56 MB this
+// kernel moves at n = 1e6).
+// XN = 2: the lean form for a FINITE radius.  The test is formed from the sums k_cg_step2_hp of
+// the previous iteration left (ipx_cg_args.xsums): x and p are not read either and no part2 is
+// written.  Instead the first ncomp workgroups fold one XS_SLICE-entry slice of the three raw
+// arrays each (one wave, fixed order), so that every workgroup of the consuming k_cg_step2_hp
+// folds 3 x ncomp entries, not 3 x H_ntiles.  They compare the raw partials' tag with `it` and
+// pass NaNs on when the sums are not this iteration's.
 // C16: column indices as 16-bit offsets into the tile's span (col - own[tile]; the host
 // binding builds them once per pattern), 2 bytes instead of 4 per nonzero.
 // PEER: p1 is the rank's own range of the p'Hp partials; summed over the ranks in the prologue
 // (ipx_peer_sum: workgroup 0 sends, every workgroup adds the contributions in rank order).
-template <int QS, int TN, bool NOXN2, bool C16, bool PEER>
+template <int QS, int TN, int XN, bool C16, bool PEER>
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_cg_step1_ar(int n, double *st, int parity, const double *__restrict__ p1, int np1,
               const double *__restrict__ x, const double *__restrict__ p,
@@ -749,7 +850,10 @@ k_cg_step1_ar(int n, double *st, int parity, const double *__restrict__ p1, int 
               const int32_t *__restrict__ colidx, const double *__restrict__ val,
               const int32_t *__restrict__ tiles, int ntiles, const int32_t *__restrict__ own,
               double *__restrict__ w, double *__restrict__ part2,
-              const uint16_t *__restrict__ col16, typename peer_arg<PEER>::type pj) {
+              const uint16_t *__restrict__ col16, typename peer_arg<PEER>::type pj,
+              const double *__restrict__ xs_raw, int nraw, double *__restrict__ xs_comp,
+              int ncomp, int it) {
+  constexpr bool NOXN2 = XN != 0;
   __shared__ double prod[TN];
   __shared__ double span[QS * IPX_BLOCK];
   __shared__ int rp[IPX_SPMV_TILE_ROWS + 1];
@@ -791,10 +895,34 @@ k_cg_step1_ar(int n, double *st, int parity, const double *__restrict__ p1, int 
     sxv[k] = NOXN2 ? 0.0 : x[col];
     spv[k] = NOXN2 ? 0.0 : p[col];
   }
+  // XN = 2: this workgroup's slice of the carried sums' raw partials, one entry per lane of
+  // the first wave and array (tile < ncomp <= ceil(nraw / XS_SLICE): the slice is not empty)
+  double xq[3] = {0.0, 0.0, 0.0}, xtag = 0.0;
+  const bool folds = XN == 2 && tile < ncomp && tid < XS_SLICE;
+  if (folds) {
+    const int i = tile * XS_SLICE + tid;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const double ld = xs_raw[q * nraw + min(i, nraw - 1)];
+      xq[q] = i < nraw ? ld : 0.0;
+    }
+    xtag = xs_raw[3 * nraw];
+  }
   if (!PEER && stop != 0.0) return;                  // (PEER: see k_cg_step2_hp)
   if (PEER && stop == 7.0) return;
   CG_STAMP(9);
   const bool lead = tile == 0 && tid == 0;
+  if (folds) {                                       // (wave-uniform: tid < 64)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) xq[q] = ipx_wave_sum(xq[q]);
+    // sums that are not this iteration's (tag != it) go on as NaNs: the consumer then decides
+    // nothing (stop code 10)
+    const bool mine = xtag == (double)it;
+    if (tid == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) xs_comp[q * XS_STRIDE + tile] = mine ? xq[q] : __builtin_nan("");
+    }
+  }
   double fout[1];
   fold.finish(fparts, fcounts, lds, fout);
   if constexpr (PEER) {
@@ -901,11 +1029,13 @@ k_compact_partials(CompactJob job, const double *__restrict__ guard) {
 }
 
 // First / last hmax entries of p for every row tile of H (both parities): what
-// k_cg_step2_hp reads as its halo.  Launched by the unfused producers of p.
+// k_cg_step2_hp reads as its halo.  Launched by the unfused producers of p -- who leave no
+// carried sums for the radius test: xs_tag (ipx_cg_args.xsums' tag, or NULL) is cleared.
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_cg_save_pb(const double *__restrict__ p, const int32_t *__restrict__ tiles, int ntiles,
-             int hmax, double *__restrict__ pb) {
+             int hmax, double *__restrict__ pb, double *__restrict__ xs_tag) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx == 0 && xs_tag) *xs_tag = 0.0;
   if (idx >= ntiles * 2 * hmax) return;
   const int t = idx / (2 * hmax), j = idx - t * 2 * hmax;
   const int r0 = tiles[t], r1 = tiles[t + 1];
@@ -913,6 +1043,9 @@ k_cg_save_pb(const double *__restrict__ p, const int32_t *__restrict__ tiles, in
   pb[idx] = v;
   pb[(int64_t)ntiles * 2 * hmax + idx] = v;
 }
+
+// Voids the tag of the carried sums (ipx_cg_args.xsums) on the stream.
+__global__ void k_xsums_void(double *xs_tag) { *xs_tag = 0.0; }
 
 // Partitioned row-sharded loop (ipsolver/sharded.py): up to four sub-ranges of partial
 // arrays -- the entries produced by a rank's OWN tiles / workgroups -- summed in a fixed
@@ -1066,6 +1199,10 @@ int ipx_cg_vec_grid(int64_t n) { return ipx_grid_for(n, VB * 2, 512); }
 static bool fused_hp(const ipx_cg_args *a) {
   return a->pb != nullptr && a->H_hmax > 0 && !a->H_operator;
 }
+// the tag of the carried sums (ipx_cg_args.xsums), NULL without them
+static double *xsums_tag(const ipx_cg_args *a) {
+  return a->xsums ? a->xsums + 3 * a->H_ntiles : nullptr;
+}
 
 // Unfused H.p; when the fused step2+H.p kernel is in use it also saves the tile
 // boundaries of the p it was given (that kernel's halo source).
@@ -1106,7 +1243,7 @@ static int launch_hp(const ipx_cg_args *a, const double *guard, hipStream_t st) 
   if (rc || !fused_hp(a)) return rc;
   const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
   hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0, st,
-                     a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb);
+                     a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb, xsums_tag(a));
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
@@ -1177,13 +1314,27 @@ static int part3_count(const ipx_cg_args *a) {
   return (a->solver_kind == 0 && a->At_vown && a->At_qv > 0) ? part4_count(a) : (int)a->At_ntiles;
 }
 
+// folded entries per carried sum (ipx_cg_args.xsums): one per XS_SLICE row tiles of H
+static int xsums_ncomp(const ipx_cg_args *a) {
+  return (int)((a->H_ntiles + XS_SLICE - 1) / XS_SLICE);
+}
+// the radius test of this block's iterations can be formed from the carried sums: both fused
+// kernels (fused step1 implies no box), a finite radius, and enough workgroups in the fused
+// step1 to fold the raw partials
+static bool xsums_on(const ipx_cg_args *a) {
+  return a->xsums != nullptr && fused_ar(a) && fused_hp(a) && a->no_radius == 0 &&
+         xsums_ncomp(a) <= (int)a->A_ntiles && xsums_ncomp(a) <= XS_STRIDE;
+}
+
 // step1 + A.r in one launch (see k_cg_step1_ar): r_next <- r + alpha Hp, w <- A r_next
 // no_xn2: trust radius +inf and no box -- ||x + alpha p||^2 is not formed at all (it can only
 // feed a comparison that is always false): x and p are not read, 16 of the kernel's 56 MB at
 // n = 1e6
+// carried (a finite radius, neither): the lean form that folds the carried sums' raw partials
+// instead (ipx_cg_args.xsums; see k_cg_step1_ar XN = 2)
 static int launch_step1_ar(const ipx_cg_args *a, int it, const double *p1, int np1,
                            hipStream_t st, bool no_xn2 = false,
-                           const ipx_peer_job *peer = nullptr) {
+                           const ipx_peer_job *peer = nullptr, bool carried = false) {
   const dim3 grid(ipx_xcd_grid((int)a->A_ntiles)), block(IPX_BLOCK);
   const ipx_peer_job pj = peer ? *peer : ipx_peer_job{};
   const ipx_no_peer none{};
@@ -1191,17 +1342,22 @@ static int launch_step1_ar(const ipx_cg_args *a, int it, const double *p1, int n
   (int)a->n, a->state, it & 1, p1, np1, a->x, a->p, a->r, a->r_next,                       \
       a->Hp, a->A_rowptr, a->A_colidx, a->A_val, a->A_tiles, (int)a->A_ntiles, a->A_own,   \
       a->w, a->part2, (const uint16_t *)a->A_col16
+  const int nraw = (int)a->H_ntiles, ncomp = xsums_ncomp(a);
+  if (carried && (peer || no_xn2 || !a->xsums)) return IPX_EINVAL;
+#define XS_NONE nullptr, 0, nullptr, 0, it
   const int qs = (int)((a->A_span + IPX_BLOCK - 1) / IPX_BLOCK);
   if (a->A_tile_nnz != 0) return IPX_EINVAL;    // (the 1024-nonzero tile form was removed)
   if (peer && !a->A_col16) return IPX_EINVAL;   // (see peer_fusable)
 #define GO(Q)                                                                              \
   do {                                                                                     \
-    if (peer && no_xn2) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, true, true, true>), grid, block, 0, st, FUSED_ARGS, pj); \
-    else if (peer) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, false, true, true>), grid, block, 0, st, FUSED_ARGS, pj); \
-    else if (no_xn2 && a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, true, true, false>), grid, block, 0, st, FUSED_ARGS, none); \
-    else if (no_xn2) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, true, false, false>), grid, block, 0, st, FUSED_ARGS, none); \
-    else if (a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, false, true, false>), grid, block, 0, st, FUSED_ARGS, none); \
-    else hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, false, false, false>), grid, block, 0, st, FUSED_ARGS, none);    \
+    if (peer && no_xn2) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 1, true, true>), grid, block, 0, st, FUSED_ARGS, pj, XS_NONE); \
+    else if (peer) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 0, true, true>), grid, block, 0, st, FUSED_ARGS, pj, XS_NONE); \
+    else if (carried && a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 2, true, false>), grid, block, 0, st, FUSED_ARGS, none, a->xsums, nraw, a->xsums + 3 * nraw + 1, ncomp, it); \
+    else if (carried) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 2, false, false>), grid, block, 0, st, FUSED_ARGS, none, a->xsums, nraw, a->xsums + 3 * nraw + 1, ncomp, it); \
+    else if (no_xn2 && a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 1, true, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE); \
+    else if (no_xn2) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 1, false, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE); \
+    else if (a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 0, true, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE); \
+    else hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 0, false, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE);    \
   } while (0)
   switch (qs) {
     case 1: case 2: GO(2); break;
@@ -1211,6 +1367,7 @@ static int launch_step1_ar(const ipx_cg_args *a, int it, const double *p1, int n
     default: return IPX_EINVAL;
   }
 #undef GO
+#undef XS_NONE
 #undef FUSED_ARGS
   IPX_CHECK_LAUNCH();
   return IPX_OK;
@@ -1221,8 +1378,13 @@ static int launch_step1_ar(const ipx_cg_args *a, int it, const double *p1, int n
 static int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double *p2, int np2,
                            const double *p3, int np3, const double *p4, int np4,
                            hipStream_t st, const double *g = nullptr,
-                           const ipx_peer_job *peer = nullptr) {
+                           const ipx_peer_job *peer = nullptr,
+                           const ipx_xsums_job *xsj = nullptr) {
   if (!g) g = a->r;
+  // (no job given: the kernel without the carried sums)
+  const ipx_xsums_job xs = xsj ? *xsj : ipx_xsums_job{nullptr, nullptr, it, 0};
+  const bool xsum = xs.raw != nullptr && (xs.write != 0 || (mode & 4) != 0);
+  if ((mode & 4) && (!xsum || !xs.in || peer || a->lb)) return IPX_EINVAL;
   const ipx_peer_job pj = peer ? *peer : ipx_peer_job{};
   const ipx_no_peer none{};
   double *g_halo = peer ? a->r : nullptr;
@@ -1244,12 +1406,14 @@ static int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double 
   if (peer && !c16) return IPX_EINVAL;                        // (see peer_fusable)
 #define GO(D, QQ, QSS)                                                                       \
   do {                                                                                       \
-    if (peer && box) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, true, true>), grid, block, 0, st, FUSED_ARGS, pj, g_halo); \
-    else if (peer) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, true>), grid, block, 0, st, FUSED_ARGS, pj, g_halo); \
-    else if (box && c16) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, true, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo); \
-    else if (box) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, false, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo); \
-    else if (c16) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo); \
-    else hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, false, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo);    \
+    if (peer && box) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, true, true>), grid, block, 0, st, FUSED_ARGS, pj, g_halo, xs); \
+    else if (peer) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, true>), grid, block, 0, st, FUSED_ARGS, pj, g_halo, xs); \
+    else if (box && c16) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, true, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
+    else if (box) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, false, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
+    else if (c16 && xsum) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, false, true>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
+    else if (xsum) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, false, false, true>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
+    else if (c16) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
+    else hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, false, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs);    \
   } while (0)
   if (a->H_diag) {
     if (small) GO(true, 3, 3); else GO(true, 4, 5);
@@ -1617,7 +1781,8 @@ int ipx_cg_save_pb(const ipx_cg_args *a, void *stream) {
   if (!fused_hp(a)) return IPX_OK;
   const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
   hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0,
-                     (hipStream_t)stream, a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb);
+                     (hipStream_t)stream, a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb,
+                     xsums_tag(a));
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
@@ -2062,7 +2227,7 @@ int ipx_cg_hp(const ipx_cg_args *a, void *stream) {
 // The fused step2 + H.p kernel on its own (iteration `it`, step2 mode bits as
 // in ipx_cg_resume); IPX_EINVAL when the argument block does not enable it.
 int ipx_cg_step2_hp(const ipx_cg_args *a, int32_t it, int32_t mode, void *stream) {
-  if (!a || !fused_hp(a)) return IPX_EINVAL;
+  if (!a || !fused_hp(a) || (mode & ~3)) return IPX_EINVAL;   // (bit 4: ipx_cg_iterate's alone)
   hipStream_t st = (hipStream_t)stream;
   // long partial arrays are compacted first, as in the loop (cg_iterate): every workgroup folds
   // all of them, and at n = 1.6e7 the 6000 uncompacted ||g||^2 partials doubled what a
@@ -2199,7 +2364,8 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
     if (fused_hp(a)) {
       const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
       hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0,
-                         st, a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb);
+                         st, a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb,
+                         xsums_tag(a));
       IPX_CHECK_LAUNCH();
     }
     return IPX_OK;
@@ -2209,6 +2375,12 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
   ipx_csr_view At{(int)a->n, (int)a->m, a->At_rowptr, a->At_colidx, a->At_val, a->At_tiles, (int)a->At_ntiles};
 #define MARK(i) do { if (ev) (void)hipEventRecord(ev[i], st); } while (0)
   int np4 = 1;
+  // a batch whose fused step2 + H.p launches run without the carried sums (trust radius +inf)
+  // changes x and p and leaves none: their tag is void from here on (one launch per batch)
+  if (a->xsums && !xsums_on(a) && it_end > it_begin) {
+    hipLaunchKernelGGL(k_xsums_void, dim3(1), dim3(1), 0, st, xsums_tag(a));
+    IPX_CHECK_LAUNCH();
+  }
   for (int it = it_begin; it < it_end; ++it) {
     MARK(0);
     int rc, np3 = (int)a->At_ntiles;
@@ -2221,11 +2393,18 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
     // trust radius +inf, no box (fused step1 implies no box): the radius / box tests of
     // qp_subproblem.py:583,599 cannot trigger; their sums are neither formed nor folded
     const bool no_xn2 = fuse1 && a->no_radius != 0;
+    // a finite radius: the test is formed from the sums the previous iteration's fused step2 +
+    // H.p kernel left (ipx_cg_args.xsums) -- inside a batch, or where the caller vouches for
+    // the batch before; the fused step1 then reads neither x nor p.  The first iteration of a
+    // call reads them as before.
+    const bool xs_on = xsums_on(a);
+    const bool carried = xs_on && (it > it_begin || a->xsums_carry != 0);
     rc = cmp.launch(guard, st);
     if (rc) return rc;
     if (fuse1) {
       MARK(1);
-      rc = launch_step1_ar(a, it, p1, np1, st, no_xn2);   // r_next = r + alpha Hp;  w = A r_next
+      // r_next = r + alpha Hp;  w = A r_next
+      rc = launch_step1_ar(a, it, p1, np1, st, no_xn2, nullptr, carried);
       if (rc) return rc;
       MARK(2);
     } else if (a->m > 0 && box_project(a)) {
@@ -2290,7 +2469,9 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
     }
     const double *p2 = a->part2, *p3 = a->part3, *p4 = a->part4;
     int np2 = part2_count(a), n4 = np4;
-    if (!no_xn2) cmp.add(p2, np2, 2, 1024);
+    // (carried: the folded sums in part2's place)
+    const double *xin = carried ? a->xsums + 3 * a->H_ntiles + 1 : nullptr;
+    if (!no_xn2 && !carried) cmp.add(p2, np2, 2, 1024);
     if (a->m > 0) {
       cmp.add(p3, np3, 2, 2048);
       cmp.add(p4, n4, 1, 1024);
@@ -2299,8 +2480,9 @@ static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hi
     if (rc) return rc;
     if (fused_hp(a)) {
       MARK(6);
-      rc = launch_step2_hp(a, it, (a->m > 0 ? 0 : 2) | (no_xn2 ? 1 : 0), p2, np2,
-                           p3, np3, p4, n4, st, a->r);
+      const ipx_xsums_job xs{a->xsums, xin, it, xs_on ? 1 : 0};
+      rc = launch_step2_hp(a, it, (a->m > 0 ? 0 : 2) | (no_xn2 ? 1 : 0) | (carried ? 4 : 0), p2, np2,
+                           p3, np3, p4, n4, st, a->r, nullptr, &xs);
       if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, guard, st);
     } else {
       hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,

@@ -241,6 +241,9 @@ def load():
 #   no-compact-groups  box-Schur group tables in their general form (44 B per variable)
 #   no-affine-groups   ... with the column table read instead of computed
 #   keep-xn2           ||x + alpha p||^2 formed even for an infinite trust radius
+#   read-xn2           finite trust radius: ||x + alpha p||^2 formed from x and p in every
+#                      iteration (no sums carried over from the fused step2 + H.p kernel:
+#                      ipx_cg_args.xsums stays NULL)
 #   pack-comm          sharded loop: the collectives in pack kernels of their own (5 launches)
 #   no-post-tail       barrier problems: the per-item back substitution as a launch of its own
 #                      (k_pairs_post) instead of as the tail of the Schur solve's kernel
@@ -253,7 +256,7 @@ def load():
 #   no-lowrank-loop    a quasi-Newton Hessian term applied by the host between the CG loop's
 #                      iterations (the operator form) instead of inside its launches
 DEBUG_FORMS = ("no-fuse", "no-resident", "no-compact-groups", "no-affine-groups", "keep-xn2",
-               "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop")
+               "read-xn2", "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop")
 
 
 def debug_form(name):

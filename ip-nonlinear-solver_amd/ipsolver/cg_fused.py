@@ -46,7 +46,8 @@ class CgArgs(ctypes.Structure):
         ("A_off16", _P), ("A_rowfirst", _P), ("A_rl", _I64), ("P_win", _P), ("P_nspan", _I64),
         ("P_navn", _I64), ("H_operator", _I64),
         ("resident", _I64), ("R_ll", _P), ("R_hw", _I64), ("R_seq", _P),
-        ("LR_W", _P), ("LR_state", _P), ("LR_part", _P), ("LR_mem", _I64), ("LR_rows", _I64))]
+        ("LR_W", _P), ("LR_state", _P), ("LR_part", _P), ("LR_mem", _I64), ("LR_rows", _I64),
+        ("xsums", _P), ("xsums_carry", ctypes.c_int32))]
 
 
 # Counters over the life of the process (diagnostics: how often the device loop
@@ -57,7 +58,8 @@ STATS = {"calls": 0, "iterations": 0, "batches": 0, "box_events": 0, "refine_eve
          "host_primed_directly": 0,   # calls that skipped the device priming after such a retry
          "resident_calls": 0,     # solves whose batches ran as resident launches (csrc/resident.hip)
          "resident_fallbacks": 0, # batches repeated on the separate launches (stop code 8)
-         "operator_calls": 0}     # solves whose Hessian was an operator applied by the host
+         "operator_calls": 0,     # solves whose Hessian was an operator applied by the host
+         "radius_undecided": 0}   # radius tests the carried sums left to the host (stop code 10)
 
 
 def _hessian_parts(H):
@@ -517,6 +519,9 @@ class _Loop:
             self.ell_row, self.ell_val = ell_rows(At, self.row_rel)
             a.At_ell_row, a.At_ell_val = _ptr(self.ell_row), _ptr(self.ell_val)
         a.no_radius = 0
+        a.xsums_carry = 0
+        if self.xsums is not None:
+            self.xsums.zero_()          # (no tag survives into another call's x and p)
         self.x = torch.empty(self.n, dtype=torch.float64, device=self.state.device)
         a.x = _ptr(self.x)
         self.keep = (A, At, Hc, Hd, lb, ub, P, LR)
@@ -544,6 +549,7 @@ class _Loop:
     def __init__(self, H, P, lb, ub, resident=None):
         from .dense import DeviceDense
         self.geometry, self.pcr_L, self.operator = None, None, None
+        self.xsums = None
         if isinstance(P.A, DeviceDense):
             self._init_dense(H, P, lb, ub)
             return
@@ -629,6 +635,13 @@ class _Loop:
                 a.part2 = _ptr(self.part2)
             self.A_col16 = own_columns16(A.pattern)
             a.A_col16 = _ptr(self.A_col16)
+            # both fused kernels: the radius test of :583 from sums the fused step2 + H.p
+            # kernel carries over to the next iteration (ipx_cg_args.xsums; the fused step1
+            # then reads neither x nor p).  Debug form read-xn2: the test reads them as before.
+            if hmax > 0 and not _hip.debug_form("read-xn2"):
+                nt = Hc.pattern.ntiles
+                self.xsums = torch.zeros(3 * nt + 1 + 3 * 256 + 1, dtype=f64, device=dev)
+                a.xsums = _ptr(self.xsums)
         # tridiagonal A A' on the single-launch solve: g = r - A'v rides in that launch
         if a.solver_kind == 0 and not no_fuse:
             geo = (ctypes.c_int32 * 2)()
@@ -977,8 +990,14 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
         first_batch = _fb
         batch_cap = 64 if L.operator is None else 8   # (an operator is applied once per
                                                       #  enqueued iteration, stopped or not)
+        carry_at = None          # where a batch on the separate launches ended without a stop
+
         def iterate(self, it, end):
             self.last = (it, end)
+            # the radius test of the batch's first iteration may use the sums the previous
+            # batch's last iteration carried over: it ended exactly here, read as stop 0,
+            # and nothing has run on the loop object since
+            carry, self.carry_at = self.carry_at == it, None
             if getattr(L, "enqueued", None) is not None:
                 done, L.enqueued = L.enqueued, None
                 if done == (it, end):        # (enqueued with the priming: ipx_cg_prime)
@@ -986,7 +1005,11 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
                 raise _hip.IpxError("device loop: the batch enqueued with the priming %r is not "
                                     "the one the driver asks for %r" % (done, (it, end)))
             if L.operator is None:
-                _hip.check(lib.ipx_cg_iterate(L.ref(), it, end, st), "ipx_cg_iterate")
+                L.args.xsums_carry = 1 if carry else 0
+                try:
+                    _hip.check(lib.ipx_cg_iterate(L.ref(), it, end, st), "ipx_cg_iterate")
+                finally:
+                    L.args.xsums_carry = 0
             else:
                 # the operator is applied between the iterations (after a stop: on unchanged
                 # p, harmless); the branches of the iterations were still taken on the device
@@ -995,10 +1018,13 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
                     L.apply_operator()
 
         def read_state(self):
-            if pending[0] is not None:
+            mine = pending[0] is None
+            if not mine:
                 s, pending[0] = list(pending[0]), None
             else:
                 s = dv.read_doubles(L.state, L.state.numel())
+            if mine and int(s[ST_STOP]) == 0 and not L.args.resident and L.xsums is not None:
+                self.carry_at = self.last[1]
             if fast and int(s[ST_STOP]) == 9:
                 # the device's verdict on the priming: the host must do it (nothing of the
                 # call's inputs was overwritten; the loop's launches were no-ops)
@@ -1051,9 +1077,11 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
             return DVec.zeros(n)
 
         def resume(self, it_stop, mode):
+            self.carry_at = None
             return _resume(lib, L, it_stop, mode, st)
 
         def refine(self, it_stop):
+            self.carry_at = None
             _refine(P, L, DVec(L.g_tensor(it_stop)))
 
     x, niter, stop_cond, hits_boundary = run_device_loop(
@@ -1113,6 +1141,11 @@ def run_device_loop(D, counters, lb, ub, trust_radius, max_iter, max_infeasible_
             D.set_x(qp.reinforce_box_boundaries(xf, lb, ub))
             stop_cond, hits_boundary = 3, True
             break
+        undecided = stop == 10            # the carried sums left the test of :583 to the host
+        if undecided:
+            counters["radius_undecided"] = counters.get("radius_undecided", 0) + 1
+            if dv.norm(D.X().add_scaled(D.Pv(), alpha)) >= trust_radius:      # :580,583
+                stop = 2
         if stop == 2:                     # :583-596
             X, Pv = D.X(), D.Pv()
             _, theta, hit = qp.box_sphere_intersections(X, Pv, lb, ub, trust_radius,
@@ -1138,6 +1171,7 @@ def run_device_loop(D, counters, lb, ub, trust_radius, max_iter, max_infeasible_
                 last_viol_it = -2
             if counter > max_infeasible_iter:
                 break
+        if stop == 5 or undecided:
             mode = 1
             # the orthogonality check has not run yet for this iteration
             s = D.resume(it_stop, mode)
@@ -1149,7 +1183,10 @@ def run_device_loop(D, counters, lb, ub, trust_radius, max_iter, max_infeasible_
         if stop == 6:                     # projections.py:72-78 refinement
             counters["refine_events"] += 1
             D.refine(it_stop)
-            s = D.resume(it_stop, mode | 2)
+            # (the device raises stop 6 only behind the radius and box tests of the same
+            # iteration, which passed: they are not repeated -- after a carried radius test
+            # the ||x + alpha p||^2 partials they would fold were not even written)
+            s = D.resume(it_stop, mode | 3)
             it = it_stop + 1
             continue
         if stop == 7:
