@@ -34,6 +34,17 @@
 //
 // Because x is only advanced in step2, every early exit leaves (x, p, alpha)
 // exactly as the reference's exit paths (:565-576, :585-596) need them.
+//
+// Host side (behind the kernels):
+//   LoopPlan  which form each stage takes for an argument block and how many partials it
+//             leaves, derived ONCE per entry-point call (plan_of) and passed down by reference
+//   tables    the instantiations of k_cg_step1_box / k_cg_step1_ar / k_cg_step2_hp, each set
+//             written out once with the reason beside what is absent
+//   halves    launch_projection_half (step1 .. g = r - A'v) and launch_update_half (compaction,
+//             step2, H.p, low-rank tail, tile boundaries of p): the batch loop, both forms of
+//             the sharded segment, ipx_cg_resume and ipx_cg_step2_hp call them with their own
+//             data (HalfArgs).  A new step1 or solve form is a value of the plan's enums and an
+//             arm of one half.
 #include "ipx_common.h"
 #include <algorithm>
 #include <vector>
@@ -1166,81 +1177,245 @@ k_cg_pack_comm(RangeJob job, double *__restrict__ out, ipx_peer_view pv, uint32_
   if (!ok) st[ST_STOP] = 7.0;
 }
 
-static int step1_box_rounds(const ipx_boxschur_args *b) {
+// ================================ host side ================================================
+// (structure: see the head of this file)
+
+// step1: k_cg_step1 | k_cg_step1_box, the front of the box-Schur projection | k_cg_step1_ar,
+// step1 inside the A.r SpMV (banded A, no box)
+enum Step1Form { S1_VECTOR, S1_BOX, S1_FUSED_AR };
+// projection: m = 0, g = r | box-Schur, the box rows never multiplied as matrix rows | banded
+// solve with g = r - A'v as its tail (one launch) | banded or box-Schur solve, then the A' SpMV |
+// dense matvecs w = A r, v = G^-1 w, g = r - A'v, t = A g
+enum ProjForm { PJ_NONE, PJ_BOX, PJ_SOLVE_TAIL, PJ_SOLVE_SPMV, PJ_DENSE };
+// step2: k_cg_step2, then H.p | k_cg_step2_hp, step2 inside the H.p SpMV (banded H)
+enum Step2Form { S2_VECTOR, S2_FUSED_HP };
+// H.p: the caller's, between the iterations | a low-rank term (+ diagonal) alone | row-major
+// n x n in H_val | CSR
+enum HpForm { HP_OPERATOR, HP_LOWRANK, HP_DENSE, HP_CSR };
+
+struct LoopPlan {
+  Step1Form step1;
+  ProjForm proj;
+  Step2Form step2;
+  HpForm hp;
+  bool fused_hp;        // the block enables k_cg_step2_hp (the dense loop still runs the vector step2)
+  bool lowrank_tail;    // a low-rank term rides behind the dense / CSR H.p (csrc/lowrank.hip)
+  bool no_xn2;          // radius +inf and no box: ||x + alpha p||^2 is neither formed nor folded
+  // the radius test of this block's iterations can be formed from the carried sums
+  // (ipx_cg_args.xsums): both fused kernels (fused step1 implies no box), a finite radius, and
+  // enough workgroups in the fused step1 to fold the raw partials
+  bool xsums;
+  int xs_ncomp;         // folded entries per carried sum: one per XS_SLICE row tiles of H
+  // entries per half of part1 .. part4:
+  int np1;              // row tiles of a CSR Hessian / workgroups of the dense or low-rank product
+  int np2;              // row tiles of A (fused step1), blocks of k_cg_step1_box, or vector chunks
+  int np3;              // row tiles of A', or workgroups of whatever forms g with its solve
+  int np4;              // workgroups of the solve's residual (||A g||^2)
+};
+
+// workgroups of a dense matvec (csrc/dense.hip): rows / 4, capped
+int dense_grid(int64_t rows) { return (int)std::min<int64_t>((rows + 3) / 4, 2048); }
+
+int step1_box_rounds(const ipx_boxschur_args *b) {
   return ipx_balanced_rounds(b->ng + b->ngen, SB_RMIN, 2 * SB_ITEMS);
 }
-template <bool PEER>
-static void launch_step1_box(const ipx_cg_args *a, const ipx_boxschur_args *b, int it,
-                             const double *p1, int np1, int nblk, const OwnRanges &own,
-                             typename peer_arg<PEER>::type pj, hipStream_t st) {
-  const ipx_group_tab T = ipx_boxschur_tab(b);
-#define IPX_S1BOX(M)                                                                            \
-  hipLaunchKernelGGL((k_cg_step1_box<PEER, M>), dim3(ipx_xcd_grid(nblk)), dim3(IPX_BLOCK), 0,  \
-                     st, a->state, it & 1, p1, np1, a->x, a->p, a->r, a->Hp, a->lb, a->ub,     \
-                     a->part2, nblk, (int)b->ng, (int)b->ngen, T, b->gen_cols, (int)b->ny,     \
-                     b->up, own, step1_box_rounds(b), pj)
-  switch (ipx_group_mode(T)) {
-    case IPX_GROUPS_AFFINE: IPX_S1BOX(IPX_GROUPS_AFFINE); break;
-    case IPX_GROUPS_UNIT: IPX_S1BOX(IPX_GROUPS_UNIT); break;
-    default: IPX_S1BOX(IPX_GROUPS_FULL);
+
+LoopPlan plan_of(const ipx_cg_args *a) {
+  LoopPlan P{};
+  const bool dense = a->solver_kind == 2;
+  const bool lowrank = a->LR_W != nullptr && !a->H_operator;
+  P.hp = a->H_operator ? HP_OPERATOR
+         : (lowrank && !a->H_rowptr && !a->H_val) ? HP_LOWRANK
+         : (dense && !a->H_rowptr) ? HP_DENSE : HP_CSR;
+  P.lowrank_tail = lowrank && (P.hp == HP_DENSE || P.hp == HP_CSR);
+  P.np1 = a->H_operator ? 1                      // [unused, p'Hp] written by the caller
+          : lowrank ? ipx_lowrank_grid(a->LR_rows)
+          : P.hp == HP_DENSE ? dense_grid(a->n) : (int)a->H_ntiles;
+  P.xs_ncomp = (int)((a->H_ntiles + XS_SLICE - 1) / XS_SLICE);
+  P.fused_hp = a->pb != nullptr && a->H_hmax > 0 && !a->H_operator;
+  if (dense) {
+    // dense Jacobian (`banded` = G^-1 in device memory, not a handle): the vector kernels
+    // around the dense matvecs, whose workgroups leave the partials
+    P.step1 = S1_VECTOR; P.proj = PJ_DENSE; P.step2 = S2_VECTOR;
+    P.np2 = (int)a->vec_grid; P.np3 = dense_grid(a->n); P.np4 = dense_grid(a->m);
+    return P;
   }
-#undef IPX_S1BOX
+  const bool fused_ar = a->r_next != nullptr && a->A_own != nullptr && a->A_span > 0 && !a->lb &&
+                        a->m > 0;
+  // solver_kind 1 with the group tables present: the fused box-Schur projection
+  const ipx_boxschur_args *b = a->solver_kind == 1 ? (const ipx_boxschur_args *)a->banded : nullptr;
+  const bool box = b && a->m > 0 && !fused_ar && b->gcol != nullptr && b->grp != nullptr &&
+                   b->up != nullptr;
+  const bool tail = a->solver_kind == 0 && a->At_vown && a->At_qv > 0;
+  P.step1 = fused_ar ? S1_FUSED_AR : box ? S1_BOX : S1_VECTOR;
+  P.proj = a->m <= 0 ? PJ_NONE : box ? PJ_BOX : tail ? PJ_SOLVE_TAIL : PJ_SOLVE_SPMV;
+  P.step2 = P.fused_hp ? S2_FUSED_HP : S2_VECTOR;
+  P.no_xn2 = fused_ar && a->no_radius != 0;
+  P.xsums = a->xsums != nullptr && fused_ar && P.fused_hp && a->no_radius == 0 &&
+            P.xs_ncomp <= (int)a->A_ntiles && P.xs_ncomp <= XS_STRIDE;
+  P.np4 = a->m > 0 ? ipx_banded_resid_count(a->solver_kind == 1 ? (b ? b->inner : nullptr)
+                                                                : a->banded) : 1;
+  if (box) {
+    const int64_t per = (int64_t)IPX_BLOCK * step1_box_rounds(b);
+    P.np2 = (int)((b->ng + b->ngen + per - 1) / per);
+    P.np3 = ipx_boxschur_project_count(b);
+  } else {
+    P.np2 = fused_ar ? (int)a->A_ntiles : (int)a->vec_grid;
+    P.np3 = P.proj == PJ_SOLVE_TAIL ? P.np4 : (int)a->At_ntiles;
+  }
+  return P;
 }
-}  // namespace
 
-IPX_STAMP_EXPORT(ipx_debug_stamps_cg, ipx_dbg_cg)
+// ---- kernel tables: every instantiation of the three templated loop kernels ----------------
+// One function per kernel maps the runtime choices to a kernel (NULL: no such combination).  The
+// PEER forms take the peer job where the others take an empty struct: two pointer types each.
 
-extern "C" {
-
-int ipx_cg_state_size(void) { return ST_SIZE; }
-// 2 workgroups per CU: measured best for step2 at n = 1e6 (9.3 us vs 10.8 us with 1024)
-int ipx_cg_vec_grid(int64_t n) { return ipx_grid_for(n, VB * 2, 512); }
-
-static bool fused_hp(const ipx_cg_args *a) {
-  return a->pb != nullptr && a->H_hmax > 0 && !a->H_operator;
+// k_cg_step1_box<PEER, MODE>: the three group-table forms (csrc/boxschur.hip) x PEER -- 6.
+template <bool PEER> using Step1BoxFn = decltype(&k_cg_step1_box<PEER, IPX_GROUPS_FULL>);
+template <bool PEER> Step1BoxFn<PEER> step1_box_kernel(int group_mode) {
+  switch (group_mode) {
+    case IPX_GROUPS_AFFINE: return k_cg_step1_box<PEER, IPX_GROUPS_AFFINE>;
+    case IPX_GROUPS_UNIT: return k_cg_step1_box<PEER, IPX_GROUPS_UNIT>;
+    default: return k_cg_step1_box<PEER, IPX_GROUPS_FULL>;
+  }
 }
+
+// k_cg_step1_ar<QS, FT_NNZ, XN, C16, PEER>: 8 forms x QS = 2, 4, 6, 8 (the column span of a row
+// tile in blocks of IPX_BLOCK, rounded up to even; a wider span has no kernel) -- 32.
+//   XN   0: ||x + alpha p||^2 from x and p;  1: not formed (LoopPlan.no_xn2);  2: from the
+//        carried sums, x and p not read
+//   C16  16-bit column offsets (ipx_cg_args.A_col16)
+//   one GPU   XN 0, 1, 2  x  C16 0, 1
+//   PEER      XN 0, 1 with C16 only: peer_fusable admits no pattern without the 16-bit tables,
+//             and the carried sums are one GPU's (the ranks' test needs the all-reduced sum)
+template <bool PEER> using Step1ArFn = decltype(&k_cg_step1_ar<2, FT_NNZ, 0, true, PEER>);
+template <bool PEER, int QS> Step1ArFn<PEER> step1_ar_forms(int xn, bool c16) {
+  if constexpr (PEER) {
+    static constexpr Step1ArFn<true> K[3] = {k_cg_step1_ar<QS, FT_NNZ, 0, true, true>,
+                                  k_cg_step1_ar<QS, FT_NNZ, 1, true, true>, nullptr};
+    return c16 ? K[xn] : nullptr;
+  } else {
+    static constexpr Step1ArFn<false> K[3][2] = {
+        {k_cg_step1_ar<QS, FT_NNZ, 0, false, false>, k_cg_step1_ar<QS, FT_NNZ, 0, true, false>},
+        {k_cg_step1_ar<QS, FT_NNZ, 1, false, false>, k_cg_step1_ar<QS, FT_NNZ, 1, true, false>},
+        {k_cg_step1_ar<QS, FT_NNZ, 2, false, false>, k_cg_step1_ar<QS, FT_NNZ, 2, true, false>}};
+    return K[xn][c16 ? 1 : 0];
+  }
+}
+template <bool PEER> Step1ArFn<PEER> step1_ar_kernel(int qs, int xn, bool c16) {
+  switch ((qs + 1) / 2) {
+    case 1: return step1_ar_forms<PEER, 2>(xn, c16);
+    case 2: return step1_ar_forms<PEER, 4>(xn, c16);
+    case 3: return step1_ar_forms<PEER, 6>(xn, c16);
+    case 4: return step1_ar_forms<PEER, 8>(xn, c16);
+  }
+  return nullptr;
+}
+
+// k_cg_step2_hp<HAS_DIAG, Q, QS, BOX, C16, PEER, XSUM>: 8 forms x HAS_DIAG x (Q, QS) -- 32.
+//   (Q, QS)  (3, 3) for short row tiles -- 3 nonzeros per row -> 683 rows: 3 elements per lane,
+//            fewer registers -- else (4, 5)
+//   one GPU  BOX 0, 1  x  C16 0, 1 without XSUM;  XSUM x C16 0, 1 without BOX: the carried sums
+//            need the fused step1, which a box excludes (a box wins: XSUM is not looked at)
+//   PEER     BOX 0, 1 with C16 only (peer_fusable), never XSUM (the carried sums are one GPU's)
+template <bool PEER> using Step2HpFn = decltype(&k_cg_step2_hp<true, 4, 5, false, true, PEER>);
+template <bool PEER, bool D, int Q, int QS>
+Step2HpFn<PEER> step2_hp_forms(bool box, bool c16, bool xsum) {
+  if constexpr (PEER) {
+    if (!c16) return nullptr;
+    return box ? k_cg_step2_hp<D, Q, QS, true, true, true>
+               : k_cg_step2_hp<D, Q, QS, false, true, true>;
+  } else {
+    static constexpr Step2HpFn<false> K[3][2] = {
+        {k_cg_step2_hp<D, Q, QS, false, false, false>, k_cg_step2_hp<D, Q, QS, false, true, false>},
+        {k_cg_step2_hp<D, Q, QS, true, false, false>, k_cg_step2_hp<D, Q, QS, true, true, false>},
+        {k_cg_step2_hp<D, Q, QS, false, false, false, true>,
+         k_cg_step2_hp<D, Q, QS, false, true, false, true>}};
+    return K[box ? 1 : xsum ? 2 : 0][c16 ? 1 : 0];
+  }
+}
+template <bool PEER>
+Step2HpFn<PEER> step2_hp_kernel(bool diag, bool small, bool box, bool c16, bool xsum) {
+  if (diag)
+    return small ? step2_hp_forms<PEER, true, 3, 3>(box, c16, xsum)
+                 : step2_hp_forms<PEER, true, 4, 5>(box, c16, xsum);
+  return small ? step2_hp_forms<PEER, false, 3, 3>(box, c16, xsum)
+               : step2_hp_forms<PEER, false, 4, 5>(box, c16, xsum);
+}
+
+// ---- single launches --------------------------------------------------------------------
+
+// np2: the plan's (blocks of the kernel)
+template <bool PEER>
+int launch_step1_box(const ipx_cg_args *a, int it, const double *p1, int np1, int np2,
+                     const OwnRanges &own, typename peer_arg<PEER>::type pj, hipStream_t st) {
+  const ipx_boxschur_args *b = (const ipx_boxschur_args *)a->banded;
+  const ipx_group_tab T = ipx_boxschur_tab(b);
+  hipLaunchKernelGGL(step1_box_kernel<PEER>(ipx_group_mode(T)), dim3(ipx_xcd_grid(np2)),
+                     dim3(IPX_BLOCK), 0, st, a->state, it & 1, p1, np1, a->x, a->p, a->r, a->Hp,
+                     a->lb, a->ub, a->part2, np2, (int)b->ng, (int)b->ngen, T, b->gen_cols,
+                     (int)b->ny, b->up, own, step1_box_rounds(b), pj);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+// step1 + A.r in one launch (see k_cg_step1_ar): r_next <- r + alpha Hp, w <- A r_next.
+// no_xn2: x and p are not read, 16 of the kernel's 56 MB at n = 1e6.  carried (a finite radius,
+// no box): the lean form that folds the carried sums' raw partials instead (XN = 2).
+template <bool PEER>
+int launch_step1_ar(const ipx_cg_args *a, const LoopPlan &P, int it, const double *p1, int np1,
+                    bool no_xn2, bool carried, typename peer_arg<PEER>::type pj, hipStream_t st) {
+  if (carried && (PEER || no_xn2 || !a->xsums)) return IPX_EINVAL;
+  if (a->A_tile_nnz != 0) return IPX_EINVAL;    // (the 1024-nonzero tile form was removed)
+  const int qs = (int)((a->A_span + IPX_BLOCK - 1) / IPX_BLOCK);
+  const auto k = step1_ar_kernel<PEER>(qs, carried ? 2 : no_xn2 ? 1 : 0, a->A_col16 != nullptr);
+  if (!k) return IPX_EINVAL;      // (a wider span; PEER without the 16-bit tables: peer_fusable)
+  const int nraw = carried ? (int)a->H_ntiles : 0;
+  hipLaunchKernelGGL(k, dim3(ipx_xcd_grid((int)a->A_ntiles)), dim3(IPX_BLOCK), 0, st, (int)a->n,
+                     a->state, it & 1, p1, np1, a->x, a->p, a->r, a->r_next, a->Hp, a->A_rowptr,
+                     a->A_colidx, a->A_val, a->A_tiles, (int)a->A_ntiles, a->A_own, a->w,
+                     a->part2, (const uint16_t *)a->A_col16, pj, carried ? a->xsums : nullptr,
+                     nraw, carried ? a->xsums + 3 * nraw + 1 : nullptr,
+                     carried ? P.xs_ncomp : 0, it);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+// step2 + H.p in one launch (see k_cg_step2_hp); iteration `it` reads the halo copies of
+// parity it & 1 and leaves those of p_next in the other one.  xs.raw == NULL: the kernel
+// without the carried sums.
+template <bool PEER>
+int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double *p2, int np2,
+                    const double *p3, int np3, const double *p4, int np4,
+                    typename peer_arg<PEER>::type pj, const ipx_xsums_job &xs, hipStream_t st) {
+  const bool xsum = xs.raw != nullptr && (xs.write != 0 || (mode & 4) != 0);
+  if ((mode & 4) && (!xsum || !xs.in || PEER || a->lb)) return IPX_EINVAL;
+  // H_tile_rows: the longest tile's row count (set by the host binding)
+  const bool small = a->H_tile_rows > 0 && a->H_tile_rows + 2 * a->H_hmax <= 3 * IPX_BLOCK;
+  const bool c16 = a->H_col16 != nullptr && a->H_rowlen != nullptr;
+  const auto k = step2_hp_kernel<PEER>(a->H_diag != nullptr, small, a->lb != nullptr, c16, xsum);
+  if (!k) return IPX_EINVAL;      // (PEER without the 16-bit tables: see peer_fusable)
+  const int64_t half = a->H_ntiles * 2 * a->H_hmax;
+  const double *pb_in = a->pb + (it & 1) * half;
+  double *pb_out = a->pb + ((it + 1) & 1) * half;
+  double *g_halo = PEER ? a->r : nullptr;
+  hipLaunchKernelGGL(k, dim3(ipx_xcd_grid((int)a->H_ntiles)), dim3(IPX_BLOCK), 0, st, (int)a->n,
+                     a->state, it & 1, mode, p2, np2, p3, np3, p4, np4, a->x, a->p,
+                     (const double *)a->r, a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles,
+                     (int)a->H_ntiles, a->H_diag, a->Hp, a->part1, (int)a->H_hmax, pb_in, pb_out,
+                     (const uint16_t *)a->H_col16, a->H_rowlen, pj, g_halo, xs);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
 // the tag of the carried sums (ipx_cg_args.xsums), NULL without them
-static double *xsums_tag(const ipx_cg_args *a) {
+double *xsums_tag(const ipx_cg_args *a) {
   return a->xsums ? a->xsums + 3 * a->H_ntiles : nullptr;
 }
 
-// Unfused H.p; when the fused step2+H.p kernel is in use it also saves the tile
-// boundaries of the p it was given (that kernel's halo source).
-static bool dense_loop(const ipx_cg_args *a) { return a->solver_kind == 2; }
-// a low-rank term rides behind every H.p (csrc/lowrank.hip)
-static bool lowrank_on(const ipx_cg_args *a) { return a->LR_W != nullptr && !a->H_operator; }
-// entries per half of part1: row tiles of a CSR Hessian / workgroups of the dense matvec
-static int part1_count(const ipx_cg_args *a) {
-  if (a->H_operator) return 1;                   // [unused, p'Hp] written by the caller
-  if (lowrank_on(a)) return ipx_lowrank_grid(a->LR_rows);   // the low-rank product's workgroups
-  if (dense_loop(a) && !a->H_rowptr) {
-    const int g = (int)((a->n + 3) / 4);
-    return g > 2048 ? 2048 : g;
-  }
-  return (int)a->H_ntiles;
-}
-
-// the low-rank term behind an H.p that left Hp (has_base) or none (H is that term + diagonal)
-static int launch_lowrank(const ipx_cg_args *a, bool has_base, const double *guard, hipStream_t st) {
-  return ipx_lowrank_cg_launch(a->n, a->LR_rows, (int)a->LR_mem, a->LR_W, a->LR_state, a->LR_part,
-                               a->p, a->Hp, a->H_diag, has_base ? 1 : 0, a->part1, guard, st);
-}
-
-static int launch_hp(const ipx_cg_args *a, const double *guard, hipStream_t st) {
-  if (a->H_operator) return IPX_OK;              // the caller applies H between the iterations
-  if (lowrank_on(a) && !a->H_rowptr && !a->H_val)
-    return launch_lowrank(a, false, guard, st);  // H = low-rank term (+ diagonal)
-  if (dense_loop(a) && !a->H_rowptr) {           // dense Hessian (row major n x n in H_val)
-    int np = 0;
-    int rc = ipx_dense_gemv_launch((int)a->n, (int)a->n, a->H_val, a->n, a->p, 1.0, a->H_diag, 0.0,
-                                   nullptr, a->Hp, a->part1, &np, guard, st);
-    if (rc || !lowrank_on(a)) return rc;
-    return launch_lowrank(a, true, guard, st);
-  }
-  ipx_csr_view H{(int)a->n, (int)a->n, a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles, (int)a->H_ntiles};
-  int rc = ipx_spmv_launch(H, a->p, 1.0, a->H_diag, 0.0, nullptr, a->Hp, a->part1, guard, st);
-  if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, guard, st);
-  if (rc || !fused_hp(a)) return rc;
+// p at the row-tile boundaries of H (the fused step2 + H.p kernel reads its neighbours' OLD p
+// there) from the current a->p
+int launch_save_pb(const ipx_cg_args *a, hipStream_t st) {
   const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
   hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0, st,
                      a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb, xsums_tag(a));
@@ -1248,13 +1423,47 @@ static int launch_hp(const ipx_cg_args *a, const double *guard, hipStream_t st) 
   return IPX_OK;
 }
 
+// the low-rank term behind an H.p that left Hp (has_base) or none (H is that term + diagonal)
+int launch_lowrank(const ipx_cg_args *a, bool has_base, const double *guard, hipStream_t st) {
+  return ipx_lowrank_cg_launch(a->n, a->LR_rows, (int)a->LR_mem, a->LR_W, a->LR_state, a->LR_part,
+                               a->p, a->Hp, a->H_diag, has_base ? 1 : 0, a->part1, guard, st);
+}
+
+// Unfused H.p in the plan's form; when the fused step2 + H.p kernel is enabled it also saves the
+// tile boundaries of the p it was given (that kernel's halo source).
+int launch_hp(const ipx_cg_args *a, const LoopPlan &P, const double *guard, hipStream_t st) {
+  int rc = IPX_OK;
+  switch (P.hp) {
+    case HP_OPERATOR:
+      return IPX_OK;
+    case HP_LOWRANK:
+      return launch_lowrank(a, false, guard, st);
+    case HP_DENSE: {
+      int np = 0;
+      rc = ipx_dense_gemv_launch((int)a->n, (int)a->n, a->H_val, a->n, a->p, 1.0, a->H_diag, 0.0,
+                                 nullptr, a->Hp, a->part1, &np, guard, st);
+      break;
+    }
+    case HP_CSR: {
+      ipx_csr_view H{(int)a->n, (int)a->n, a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles,
+                     (int)a->H_ntiles};
+      rc = ipx_spmv_launch(H, a->p, 1.0, a->H_diag, 0.0, nullptr, a->Hp, a->part1, guard, st);
+      break;
+    }
+  }
+  if (!rc && P.lowrank_tail) rc = launch_lowrank(a, true, guard, st);
+  if (rc || P.hp != HP_CSR || !P.fused_hp) return rc;
+  return launch_save_pb(a, st);
+}
+
 // Host side of k_compact_partials: queue arrays, launch once, hand back the
 // (pointer, entries per half) the consumer should fold.
 struct Compactor {
   const ipx_cg_args *a;
   CompactJob job;
+  const double *guard;          // the stop word, or NULL: compact whatever it says
   int n = 0, used = 0;
-  explicit Compactor(const ipx_cg_args *args) : a(args) { job.first[0] = 0; }
+  Compactor(const ipx_cg_args *args, const double *g) : a(args), guard(g) { job.first[0] = 0; }
   // returns true (and rewrites ptr / count) when the array will be compacted
   bool add(const double *&ptr, int &count, int halves, int limit) {
     if (!a->fold_ws || count <= limit || n >= 3) return false;
@@ -1269,7 +1478,7 @@ struct Compactor {
     ++n;
     return true;
   }
-  int launch(const double *guard, hipStream_t st) {
+  int launch(hipStream_t st) {
     if (n == 0) return IPX_OK;
     for (int k = n; k < 3; ++k) job.first[k + 1] = job.first[n];
     hipLaunchKernelGGL(k_compact_partials, dim3(job.first[n]), dim3(IPX_BLOCK), 0, st, job, guard);
@@ -1280,151 +1489,240 @@ struct Compactor {
   }
 };
 
-static bool fused_ar(const ipx_cg_args *a);
-static bool fused_hp(const ipx_cg_args *a);
+// ---- the two halves of an iteration -------------------------------------------------------
 
-// solver_kind 1 with the group tables present: the fused box-Schur projection
-static bool box_project(const ipx_cg_args *a) {
-  if (a->solver_kind != 1 || !a->banded) return false;
-  const ipx_boxschur_args *b = (const ipx_boxschur_args *)a->banded;
-  return b->gcol != nullptr && b->grp != nullptr && b->up != nullptr && !fused_ar(a);
-}
+// What differs between the drivers, besides where the partials a half folds come from (its
+// arguments: an array with its count, one all-reduced entry, a rank's own window of an array).
+struct HalfArgs {
+  int it;
+  // step2's mode bits: 1 no ||x + alpha p||^2 (LoopPlan.no_xn2), 2 no orthogonality test, 4 the
+  // radius test from the carried sums.  The projection half reads 1 and 4 (for its step1)
+  int mode;
+  const double *guard;                  // the stop word, for the launches that take one
+  const OwnRanges *own = nullptr;       // the rank's own entries (sharded loop); NULL: every entry
+  const ipx_peer_job *peer = nullptr;   // collectives in the kernels' prologues (sharded, fuse_comm)
+  Compactor *cmp = nullptr;             // arrays too long to fold directly are compacted first
+  // the carried sums the fused step2 + H.p writes and reads (the batch loop's alone)
+  ipx_xsums_job xs{nullptr, nullptr, it, 0};
+  hipEvent_t *ev = nullptr;             // ipx_cg_iterate_timed's events of this iteration
+};
+#define MARK(i) do { if (h.ev) (void)hipEventRecord(h.ev[i], st); } while (0)
 
-static bool fused_ar(const ipx_cg_args *a) {
-  return a->r_next != nullptr && a->A_own != nullptr && a->A_span > 0 && !a->lb && a->m > 0;
-}
-// entries per half of part2: one per row tile of A (fused step1) or per vector chunk
-static int step1_box_blocks(const ipx_cg_args *a) {
-  const ipx_boxschur_args *b = (const ipx_boxschur_args *)a->banded;
-  const int64_t per = (int64_t)IPX_BLOCK * step1_box_rounds(b);
-  return (int)((b->ng + b->ngen + per - 1) / per);
-}
-static int part4_count(const ipx_cg_args *a) {
-  return a->m > 0 ? ipx_banded_resid_count(a->solver_kind == 1
-                        ? ((const ipx_boxschur_args *)a->banded)->inner : a->banded) : 1;
-}
-static int part2_count(const ipx_cg_args *a) {
-  if (box_project(a)) return step1_box_blocks(a);
-  return fused_ar(a) ? (int)a->A_ntiles : (int)a->vec_grid;
-}
-// entries per half of part3: one per row tile of A', or per workgroup of the solve when
-// g = r - A'v is its tail
-static int part3_count(const ipx_cg_args *a) {
-  if (box_project(a)) return ipx_boxschur_project_count((const ipx_boxschur_args *)a->banded);
-  return (a->solver_kind == 0 && a->At_vown && a->At_qv > 0) ? part4_count(a) : (int)a->At_ntiles;
-}
-
-// folded entries per carried sum (ipx_cg_args.xsums): one per XS_SLICE row tiles of H
-static int xsums_ncomp(const ipx_cg_args *a) {
-  return (int)((a->H_ntiles + XS_SLICE - 1) / XS_SLICE);
-}
-// the radius test of this block's iterations can be formed from the carried sums: both fused
-// kernels (fused step1 implies no box), a finite radius, and enough workgroups in the fused
-// step1 to fold the raw partials
-static bool xsums_on(const ipx_cg_args *a) {
-  return a->xsums != nullptr && fused_ar(a) && fused_hp(a) && a->no_radius == 0 &&
-         xsums_ncomp(a) <= (int)a->A_ntiles && xsums_ncomp(a) <= XS_STRIDE;
-}
-
-// step1 + A.r in one launch (see k_cg_step1_ar): r_next <- r + alpha Hp, w <- A r_next
-// no_xn2: trust radius +inf and no box -- ||x + alpha p||^2 is not formed at all (it can only
-// feed a comparison that is always false): x and p are not read, 16 of the kernel's 56 MB at
-// n = 1e6
-// carried (a finite radius, neither): the lean form that folds the carried sums' raw partials
-// instead (ipx_cg_args.xsums; see k_cg_step1_ar XN = 2)
-static int launch_step1_ar(const ipx_cg_args *a, int it, const double *p1, int np1,
-                           hipStream_t st, bool no_xn2 = false,
-                           const ipx_peer_job *peer = nullptr, bool carried = false) {
-  const dim3 grid(ipx_xcd_grid((int)a->A_ntiles)), block(IPX_BLOCK);
-  const ipx_peer_job pj = peer ? *peer : ipx_peer_job{};
-  const ipx_no_peer none{};
-#define FUSED_ARGS                                                                         \
-  (int)a->n, a->state, it & 1, p1, np1, a->x, a->p, a->r, a->r_next,                       \
-      a->Hp, a->A_rowptr, a->A_colidx, a->A_val, a->A_tiles, (int)a->A_ntiles, a->A_own,   \
-      a->w, a->part2, (const uint16_t *)a->A_col16
-  const int nraw = (int)a->H_ntiles, ncomp = xsums_ncomp(a);
-  if (carried && (peer || no_xn2 || !a->xsums)) return IPX_EINVAL;
-#define XS_NONE nullptr, 0, nullptr, 0, it
-  const int qs = (int)((a->A_span + IPX_BLOCK - 1) / IPX_BLOCK);
-  if (a->A_tile_nnz != 0) return IPX_EINVAL;    // (the 1024-nonzero tile form was removed)
-  if (peer && !a->A_col16) return IPX_EINVAL;   // (see peer_fusable)
-#define GO(Q)                                                                              \
-  do {                                                                                     \
-    if (peer && no_xn2) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 1, true, true>), grid, block, 0, st, FUSED_ARGS, pj, XS_NONE); \
-    else if (peer) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 0, true, true>), grid, block, 0, st, FUSED_ARGS, pj, XS_NONE); \
-    else if (carried && a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 2, true, false>), grid, block, 0, st, FUSED_ARGS, none, a->xsums, nraw, a->xsums + 3 * nraw + 1, ncomp, it); \
-    else if (carried) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 2, false, false>), grid, block, 0, st, FUSED_ARGS, none, a->xsums, nraw, a->xsums + 3 * nraw + 1, ncomp, it); \
-    else if (no_xn2 && a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 1, true, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE); \
-    else if (no_xn2) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 1, false, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE); \
-    else if (a->A_col16) hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 0, true, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE); \
-    else hipLaunchKernelGGL((k_cg_step1_ar<Q, FT_NNZ, 0, false, false>), grid, block, 0, st, FUSED_ARGS, none, XS_NONE);    \
-  } while (0)
-  switch (qs) {
-    case 1: case 2: GO(2); break;
-    case 3: case 4: GO(4); break;
-    case 5: case 6: GO(6); break;
-    case 7: case 8: GO(8); break;
-    default: return IPX_EINVAL;
+// step1 in its form (folding the np1 entries of p'Hp at p1 + np1), w = A r where step1 did not
+// form it, the solve in its form, g = r - A'v where the solve did not form it.  Hands back how
+// many partials per half it left in part2, part3 and part4.
+int launch_projection_half(const ipx_cg_args *a, const LoopPlan &P, const HalfArgs &h,
+                           const double *p1, int np1, int *np2, int *np3, int *np4,
+                           hipStream_t st) {
+  MARK(0);
+  int rc;
+  if (h.cmp) {
+    h.cmp->add(p1, np1, 2, 2048);      // beyond what a consumer folds in one or two rounds
+    rc = h.cmp->launch(st);
+    if (rc) return rc;
   }
-#undef GO
-#undef XS_NONE
-#undef FUSED_ARGS
-  IPX_CHECK_LAUNCH();
+  const bool fuse1 = P.step1 == S1_FUSED_AR;
+  const OwnRanges own = h.own ? *h.own : own_all(a->n);
+  switch (P.step1) {
+    case S1_FUSED_AR:
+      MARK(1);
+      rc = h.peer ? launch_step1_ar<true>(a, P, h.it, p1, np1, h.mode & 1, h.mode & 4, *h.peer, st)
+                  : launch_step1_ar<false>(a, P, h.it, p1, np1, h.mode & 1, h.mode & 4,
+                                           ipx_no_peer{}, st);
+      if (rc) return rc;
+      MARK(2);
+      break;
+    case S1_BOX:
+      rc = h.peer ? launch_step1_box<true>(a, h.it, p1, np1, P.np2, own, *h.peer, st)
+                  : launch_step1_box<false>(a, h.it, p1, np1, P.np2, own, ipx_no_peer{}, st);
+      if (rc) return rc;
+      MARK(1);
+      break;
+    case S1_VECTOR:
+      if (h.peer) return IPX_EINVAL;                 // (no PEER form: see peer_fusable)
+      hipLaunchKernelGGL(k_cg_step1, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
+                         a->state, h.it & 1, p1, np1, a->x, a->p, a->r, a->Hp, a->lb, a->ub,
+                         a->part2, (int)a->vec_grid, own);
+      IPX_CHECK_LAUNCH();
+      MARK(1);
+      break;
+  }
+  *np2 = P.np2;
+  *np3 = P.np3;
+  *np4 = P.np4;
+  const double *r_in = fuse1 ? a->r_next : a->r;      // what g = r - A'v reads
+  switch (P.proj) {
+    case PJ_NONE:
+      break;
+    case PJ_BOX: {
+      // simple (box) rows eliminated analytically and never multiplied as matrix rows:
+      // g = r - A'(A A')^-1 A r in one call (csrc/boxschur.hip); a rank's kernels count its own
+      // entries only (element mask), so its own sums are the sums over ALL their partials
+      int32_t n3 = 0, n4 = 0;
+      rc = ipx_boxschur_project_from((const ipx_boxschur_args *)a->banded, a->r, a->r, a->part3,
+                                     &n3, a->part4, &n4, h.guard, 1, st, h.own);
+      if (rc) return rc;
+      *np3 = n3;
+      *np4 = n4;
+      MARK(2); MARK(3); MARK(4); MARK(5);
+      break;
+    }
+    case PJ_SOLVE_TAIL:
+    case PJ_SOLVE_SPMV: {
+      if (!fuse1) {
+        ipx_csr_view A{(int)a->m, (int)a->n, a->A_rowptr, a->A_colidx, a->A_val, a->A_tiles,
+                       (int)a->A_ntiles};
+        rc = ipx_spmv_launch(A, a->r, 1.0, nullptr, 0.0, nullptr, a->w, nullptr, h.guard, st);
+        if (rc) return rc;
+        MARK(2);
+      }
+      // v = (AA')^-1 w, and ||A g||^2 for the orthogonality test as the constraint-space
+      // residual ||w - (A A') v||^2 from the same launch (see k_correct_oop / k_band_residual)
+      if (P.proj == PJ_SOLVE_TAIL) {
+        // decoupled banded solve with g = r - A'v as its tail (one launch for both);
+        // ||g||^2 partials are then per workgroup of that kernel
+        rc = ipx_banded_solve_resid_atv_launch(a->banded, a->w, a->v, a->part4, np4, a->At_rowptr,
+                                               a->At_colidx, a->At_val, r_in, a->r, a->At_vown,
+                                               (int)a->At_qv, a->part3, h.guard, st,
+                                               a->At_ell_row, a->At_ell_val, a->n);
+        if (rc) return rc;
+        *np3 = *np4;
+        MARK(3);
+        MARK(4);
+      } else {
+        if (a->solver_kind == 1)    // box rows eliminated analytically, banded Schur complement
+          rc = ipx_boxschur_solve((const ipx_boxschur_args *)a->banded, a->w, a->v, a->part4, np4,
+                                  h.guard, st);
+        else
+          rc = ipx_banded_solve_resid_launch(a->banded, a->w, a->v, a->part4, np4, h.guard, st);
+        if (rc) return rc;
+        MARK(3);
+        // r = r - A'v  (g_next), partials of ||g||^2
+        ipx_csr_view At{(int)a->n, (int)a->m, a->At_rowptr, a->At_colidx, a->At_val, a->At_tiles,
+                        (int)a->At_ntiles};
+        rc = ipx_spmv_launch(At, a->v, -1.0, nullptr, 1.0, r_in, a->r, a->part3, h.guard, st);
+        if (rc) return rc;
+        MARK(4);
+      }
+      MARK(5);
+      break;
+    }
+    case PJ_DENSE: {
+      // Dense Jacobian (BASELINE config 2): A (m x n) and A' (n x m) row major in A_val /
+      // At_val, `banded` = G^-1 (M x M, M = m rounded up to 32; w and v are M long with a zero
+      // tail).  Four matvecs, whose epilogues carry the reductions: w = A r, v = G^-1 w,
+      // g = r - A'v, t = A g (the reference's orthogonality measure, projections.py:52, literally)
+      const int n = (int)a->n, m = (int)a->m, M = ((m + 31) / 32) * 32;
+      int np = 0;
+      rc = ipx_dense_gemv_launch(m, n, a->A_val, n, a->r, 1.0, nullptr, 0.0, nullptr, a->w,
+                                 nullptr, &np, h.guard, st);
+      if (rc) return rc;
+      rc = ipx_dense_gemv_launch(M, M, (const double *)a->banded, M, a->w, 1.0, nullptr, 0.0,
+                                 nullptr, a->v, nullptr, &np, h.guard, st);
+      if (rc) return rc;
+      rc = ipx_dense_gemv_launch(n, m, a->At_val, m, a->v, -1.0, nullptr, 1.0, a->r, a->r,
+                                 a->part3, np3, h.guard, st);              // g = r - A'v, ||g||^2
+      if (rc) return rc;
+      rc = ipx_dense_gemv_launch(m, n, a->A_val, n, a->r, 1.0, nullptr, 0.0, nullptr, a->t,
+                                 a->part4, np4, h.guard, st);              // ||A g||^2
+      if (rc) return rc;
+      break;
+    }
+  }
   return IPX_OK;
 }
 
-// step2 + H.p in one launch (see k_cg_step2_hp); iteration `it` reads the halo
-// copies of parity it & 1 and leaves those of p_next in the other one.
-static int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double *p2, int np2,
-                           const double *p3, int np3, const double *p4, int np4,
-                           hipStream_t st, const double *g = nullptr,
-                           const ipx_peer_job *peer = nullptr,
-                           const ipx_xsums_job *xsj = nullptr) {
-  if (!g) g = a->r;
-  // (no job given: the kernel without the carried sums)
-  const ipx_xsums_job xs = xsj ? *xsj : ipx_xsums_job{nullptr, nullptr, it, 0};
-  const bool xsum = xs.raw != nullptr && (xs.write != 0 || (mode & 4) != 0);
-  if ((mode & 4) && (!xsum || !xs.in || peer || a->lb)) return IPX_EINVAL;
-  const ipx_peer_job pj = peer ? *peer : ipx_peer_job{};
-  const ipx_no_peer none{};
-  double *g_halo = peer ? a->r : nullptr;
-  const int64_t half = a->H_ntiles * 2 * a->H_hmax;
-  const double *pb_in = a->pb + (it & 1) * half;
-  double *pb_out = a->pb + ((it + 1) & 1) * half;
-  const dim3 grid(ipx_xcd_grid((int)a->H_ntiles)), block(IPX_BLOCK);
-#define FUSED_ARGS                                                                            \
-  (int)a->n, a->state, it & 1, mode, p2, np2, p3, np3, p4, np4, a->x, a->p, g,                \
-      a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles,                                         \
-      (int)a->H_ntiles, a->H_diag, a->Hp, a->part1, (int)a->H_hmax, pb_in, pb_out,           \
-      (const uint16_t *)a->H_col16, a->H_rowlen
-  // H_hmax carries the longest tile's row count in its upper half (set by the host
-  // binding): short tiles (3 nonzeros per row -> 683 rows) take the 3-elements-per-lane
-  // instantiation, which needs fewer registers
-  const bool small = a->H_tile_rows > 0 && a->H_tile_rows + 2 * a->H_hmax <= 3 * IPX_BLOCK;
-  const bool box = a->lb != nullptr;
-  const bool c16 = a->H_col16 != nullptr && a->H_rowlen != nullptr;
-  if (peer && !c16) return IPX_EINVAL;                        // (see peer_fusable)
-#define GO(D, QQ, QSS)                                                                       \
-  do {                                                                                       \
-    if (peer && box) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, true, true>), grid, block, 0, st, FUSED_ARGS, pj, g_halo, xs); \
-    else if (peer) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, true>), grid, block, 0, st, FUSED_ARGS, pj, g_halo, xs); \
-    else if (box && c16) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, true, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
-    else if (box) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, true, false, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
-    else if (c16 && xsum) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, false, true>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
-    else if (xsum) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, false, false, true>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
-    else if (c16) hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, true, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs); \
-    else hipLaunchKernelGGL((k_cg_step2_hp<D, QQ, QSS, false, false, false>), grid, block, 0, st, FUSED_ARGS, none, g_halo, xs);    \
-  } while (0)
-  if (a->H_diag) {
-    if (small) GO(true, 3, 3); else GO(true, 4, 5);
+// Compaction of the long partial arrays, step2 in its form (folding ||x + alpha p||^2 and the
+// violations at p2, ||g||^2 at p3, ||A g||^2 at p4), H.p where step2 did not form it, the
+// low-rank tail, and the tile boundaries of p where the fused kernel will want them.
+int launch_update_half(const ipx_cg_args *a, const LoopPlan &P, const HalfArgs &h,
+                       const double *p2, int np2, const double *p3, int np3, const double *p4,
+                       int np4, hipStream_t st) {
+  int rc;
+  if (h.cmp) {
+    // every workgroup folds all of them: at n = 1.6e7 the 6000 uncompacted ||g||^2 partials
+    // doubled what a workgroup of the fused kernel reads (495 us on its own, 226 us in the loop)
+    if (!(h.mode & 5)) h.cmp->add(p2, np2, 2, 1024);       // (bit 4: the folded sums in its place)
+    h.cmp->add(p3, np3, 2, 2048);
+    if (!(h.mode & 2)) h.cmp->add(p4, np4, 1, 1024);
+    rc = h.cmp->launch(st);
+    if (rc) return rc;
+  }
+  if (P.step2 == S2_FUSED_HP) {
+    MARK(6);
+    rc = h.peer ? launch_step2_hp<true>(a, h.it, h.mode, p2, np2, p3, np3, p4, np4, *h.peer, h.xs,
+                                        st)
+                : launch_step2_hp<false>(a, h.it, h.mode, p2, np2, p3, np3, p4, np4,
+                                         ipx_no_peer{}, h.xs, st);
+    if (!rc && P.lowrank_tail) rc = launch_lowrank(a, true, h.guard, st);
   } else {
-    if (small) GO(false, 3, 3); else GO(false, 4, 5);
+    if (h.peer) return IPX_EINVAL;                   // (no PEER form: see peer_fusable)
+    hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
+                       a->state, h.it & 1, h.mode, p2, np2, p3, np3, p4, np4, a->x, a->p, a->r,
+                       (int)a->vec_grid);
+    IPX_CHECK_LAUNCH();
+    MARK(6);
+    rc = launch_hp(a, P, h.guard, st);
   }
-#undef GO
-#undef FUSED_ARGS
-  IPX_CHECK_LAUNCH();
+  if (rc) return rc;
+  MARK(7);
   return IPX_OK;
 }
+#undef MARK
+
+// Enqueue iterations it_begin .. it_end-1.  Never synchronises.  ev (ipx_cg_iterate_timed): eight
+// events per iteration, recorded around its kernel classes.
+int cg_iterate(const ipx_cg_args *a, const LoopPlan &P, int32_t it_begin, int32_t it_end,
+               hipStream_t st, hipEvent_t *ev) {
+  if (P.proj == PJ_DENSE) {
+    if (ev) return IPX_EINVAL;
+  } else if (!ev && it_end > it_begin && ipx_cg_resident_ok(a)) {
+    // small banded problems (one CU per workgroup of the solve): the whole batch as ONE
+    // resident launch (csrc/resident.hip), which leaves x, p, r, Hp, the state block and the
+    // partial arrays as these launches would -- the tile boundaries of p for the fused step2 +
+    // H.p kernel (an event handler's resume, a later batch on the separate launches) follow it
+    int rc = ipx_cg_resident_launch(a, it_begin, it_end, P.np1, P.np2, P.np3, P.np4, st);
+    if (rc || !P.fused_hp) return rc;
+    return launch_save_pb(a, st);
+  }
+  const double *guard = a->state + ST_STOP;
+  // a batch whose fused step2 + H.p launches run without the carried sums (trust radius +inf)
+  // changes x and p and leaves none: their tag is void from here on (one launch per batch)
+  if (a->xsums && !P.xsums && it_end > it_begin) {
+    hipLaunchKernelGGL(k_xsums_void, dim3(1), dim3(1), 0, st, xsums_tag(a));
+    IPX_CHECK_LAUNCH();
+  }
+  for (int it = it_begin; it < it_end; ++it) {
+    // a finite radius: the test is formed from the sums the previous iteration's fused step2 +
+    // H.p kernel left (ipx_cg_args.xsums) -- inside a batch, or where the caller vouches for
+    // the batch before; the fused step1 then reads neither x nor p.  The first iteration of a
+    // call reads them as before.
+    const bool carried = P.xsums && (it > it_begin || a->xsums_carry != 0);
+    Compactor cmp(a, guard);
+    HalfArgs h{it, (P.proj == PJ_NONE ? 2 : 0) | (P.no_xn2 ? 1 : 0) | (carried ? 4 : 0), guard};
+    if (P.proj != PJ_DENSE) h.cmp = &cmp;            // (the dense loop never compacted)
+    // the fused step2 + H.p writes the sums (or voids their tag) and, carried, reads the sums
+    // the fused step1 folded (in part2's place)
+    h.xs = ipx_xsums_job{a->xsums, carried ? a->xsums + 3 * a->H_ntiles + 1 : nullptr, it,
+                         P.xsums ? 1 : 0};
+    h.ev = ev;
+    int np2 = 0, np3 = 0, np4 = 0;
+    int rc = launch_projection_half(a, P, h, a->part1, P.np1, &np2, &np3, &np4, st);
+    if (rc) return rc;
+    rc = launch_update_half(a, P, h, a->part2, np2, a->part3, np3, a->part4, np4, st);
+    if (rc) return rc;
+  }
+  return IPX_OK;
+}
+}  // namespace
+
+IPX_STAMP_EXPORT(ipx_debug_stamps_cg, ipx_dbg_cg)
+
+extern "C" {
+
+int ipx_cg_state_size(void) { return ST_SIZE; }
+// 2 workgroups per CU: measured best for step2 at n = 1e6 (9.3 us vs 10.8 us with 1024)
+int ipx_cg_vec_grid(int64_t n) { return ipx_grid_for(n, VB * 2, 512); }
 
 // Single kernels of the loop with explicit partial buffers, for drivers that
 // interleave their own steps.
@@ -1448,16 +1746,6 @@ int ipx_cg_step2(int64_t n, double *state, int32_t it, int32_t mode, const doubl
   return IPX_OK;
 }
 
-// One local segment of an iteration of the PARTITIONED row-sharded loop (ipsolver/sharded.py
-// FusedShardedCG).  The argument block describes the rank's extended local problem (own
-// rows / variables plus halo copies): the kernels are those of the single-GPU loop; what is
-// specific is (a) their reduction inputs are the all-reduced scalars (e->s1, e->pack, one
-// entry each) instead of the predecessor's partial arrays, and (b) the partials they leave
-// are summed over the rank's own tiles only.
-//   phase 0 (after the all-reduce of s1): step1 (+ A.r), solve (+ g = r - A'v), own sums of
-//           ||x+ap||^2, #violations, ||g||^2, ||A g||^2 -> e->pack[0..4)
-//   phase 1 (after the all-reduce of pack and the halo exchange of g): step2 (+ H.p),
-//           own sum of p'Hp -> e->s1[1]
 static OwnRanges own_of(const ipx_shard2_ext *e) {
   OwnRanges o;
   for (int k = 0; k < 4; ++k) {
@@ -1518,8 +1806,9 @@ k_zero_outside(double *__restrict__ part, int n, OwnRanges keep) {
 }
 
 // own sum of the p'Hp partials (second half of part1) over the segments' own row tiles
-static int pack_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, hipStream_t st) {
-  const int np1 = part1_count(a);
+static int pack_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, const LoopPlan &P,
+                   hipStream_t st) {
+  const int np1 = P.np1;
   RangeJob job;
   job.npieces = (int)e->nseg;
   job.active = 2;
@@ -1534,7 +1823,7 @@ static int pack_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, hipStream_t st
   // of the batch are no-ops but their all-reduces still run; re-packing the (unchanged)
   // own sums keeps the reduced values those of the iteration that stopped
   int rc = launch_pack(a, e, job, e->s1, false, st);
-  if (rc || !e->peer || !e->fuse_comm || !box_project(a)) return rc;
+  if (rc || !e->peer || !e->fuse_comm || P.proj != PJ_BOX) return rc;
   // the prologue form of k_cg_step1_box folds ALL of part1's second half: zero the entries
   // an unfused H.p left for the tiles of halo rows
   OwnRanges keep;
@@ -1549,19 +1838,19 @@ static int pack_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, hipStream_t st
 }
 
 // The collectives INSIDE the loop's own kernels (k_cg_step1_ar / k_cg_step2_hp, PEER forms): 3
-// launches per iteration instead of 5.  One segment (x-space problems), both fused SpMV
-// kernels in their 16-bit index forms, g = r - A'v as the solve's tail, no box.
-static bool peer_fusable(const ipx_cg_args *a, const ipx_shard2_ext *e) {
+// launches per iteration instead of 5.  Both need the fused step2 + H.p kernel in its 16-bit
+// index form.
+static bool peer_fusable(const ipx_cg_args *a, const ipx_shard2_ext *e, const LoopPlan &P) {
   ipx_peer *peer = (ipx_peer *)e->peer;
   if (!(peer && e->fuse_comm && peer->view.world > 1 && peer->view.world <= IPX_MAX_PEERS &&
-        ipx_peer_ready(peer) && fused_hp(a) && a->H_col16 && a->H_rowlen && a->m > 0))
+        ipx_peer_ready(peer) && P.fused_hp && a->H_col16 && a->H_rowlen && a->m > 0))
     return false;
-  // x-space problems: both fused SpMV kernels, g = r - A'v as the solve's tail, no box
-  if (e->nseg == 1 && fused_ar(a) && !a->lb && a->A_col16 &&
-      a->solver_kind == 0 && a->At_vown && a->At_qv > 0)
+  // x-space problems: one segment, the fused step1 + A.r kernel (hence no box) in its 16-bit
+  // index form, g = r - A'v as the solve's tail
+  if (e->nseg == 1 && P.step1 == S1_FUSED_AR && a->A_col16 && P.proj == PJ_SOLVE_TAIL)
     return true;
   // the barrier problem's z-space: the projection without the box rows as matrix rows
-  return box_project(a) && a->lb != nullptr;
+  return P.proj == PJ_BOX && a->lb != nullptr;
 }
 
 // the segments' extents and their places in the mailboxes' halo areas
@@ -1583,61 +1872,52 @@ static int peer_job_geometry(const ipx_shard2_ext *e, const ipx_peer *peer, ipx_
   return (inl > cap || inr > cap || outl > cap || outr > cap) ? IPX_EINVAL : IPX_OK;
 }
 
-static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t phase,
-                          int32_t it, int32_t mode, void *stream, bool fuse_comm);
-
-int ipx_cg_shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t phase,
-                          int32_t it, int32_t mode, void *stream) {
-  return shard2_segment(a, e, phase, it, mode, stream, false);
-}
-
-static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t phase,
-                          int32_t it, int32_t mode, void *stream, bool fuse_comm) {
+// One local segment of an iteration of the PARTITIONED row-sharded loop (ipsolver/sharded.py
+// FusedShardedCG).  The argument block describes the rank's extended local problem (own
+// rows / variables plus halo copies): the halves are those of the single-GPU loop; what is
+// specific is (a) their reduction inputs are the all-reduced scalars (e->s1, e->pack, one
+// entry each) instead of the predecessor's partial arrays, and (b) the partials they leave
+// are summed over the rank's own tiles only.
+//   phase 0 (after the all-reduce of s1): the projection half, then the own sums of
+//           ||x+ap||^2, #violations, ||g||^2, ||A g||^2 -> e->pack[0..4)
+//   phase 1 (after the all-reduce of pack and the halo exchange of g): the update half, then
+//           the own sum of p'Hp -> e->s1[1]
+// fuse_comm: the collectives in the prologues of the halves' own kernels (HalfArgs.peer) -- the
+// all-reduce of p'Hp in step1's, that of the four sums and the halo exchange of g in step2's;
+// their inputs are then the rank's own windows of the partial arrays, and no pack launch runs.
+static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, const LoopPlan &P,
+                          int32_t phase, int32_t it, int32_t mode, void *stream, bool fuse_comm) {
   if (!a || !e || phase < 0 || phase > 1 || !e->s1 || !e->pack || a->solver_kind > 1 ||
       e->nseg < 1 || e->nseg > 4 || a->LR_W)
     return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  const double *guard = a->state + ST_STOP;
+  const bool boxp = P.proj == PJ_BOX;
+  const OwnRanges own = own_of(e);
+  int np2 = 0, np3 = 0, np4 = 0;
   if (fuse_comm) {
     ipx_peer *peer = (ipx_peer *)e->peer;
     ipx_peer_job pj{};
     pj.pv = peer->view;
-    const bool boxp = box_project(a);
-    const double *stopw = a->state + ST_STOP;
     if (phase == 0) {
-      // step1 with the all-reduce of p'Hp in its prologue, then the projection; no pack launch
-      const int np1 = part1_count(a);
       // (every argument check comes BEFORE the sequence numbers move: a rank that returns
       // IPX_EINVAL must not leave its counters out of step with the group's)
-      if (!boxp && (e->p1_hi[0] > np1 || e->p1_hi[0] < e->p1_lo[0])) return IPX_EINVAL;
+      if (!boxp && (e->p1_hi[0] > P.np1 || e->p1_hi[0] < e->p1_lo[0])) return IPX_EINVAL;
       if (++peer->seq == 0) ++peer->seq;
       pj.seq = peer->seq;
       ++peer->fused;
-      if (boxp) {
-        const ipx_boxschur_args *b = (const ipx_boxschur_args *)a->banded;
-        const OwnRanges own = own_of(e);
-        const int nblk = step1_box_blocks(a);
-        launch_step1_box<true>(a, b, it, a->part1, np1, nblk, own, pj, st);
-        IPX_CHECK_LAUNCH();
-        int32_t n3 = 0, n4 = 0;
-        return ipx_boxschur_project_from(b, a->r, a->r, a->part3, &n3, a->part4, &n4, stopw, 1, st,
-                                         &own);
-      }
-      const int cnt = (int)(e->p1_hi[0] - e->p1_lo[0]);
-      // (the kernel folds [p1 + np1, p1 + 2 np1): hand it the own range as that window)
-      const double *p1 = a->part1 + np1 + e->p1_lo[0] - cnt;
-      int rc = launch_step1_ar(a, it, p1, cnt, st, false, &pj);
-      if (rc) return rc;
-      int np4 = 0;
-      return ipx_banded_solve_resid_atv_launch(a->banded, a->w, a->v, a->part4, &np4, a->At_rowptr,
-                                               a->At_colidx, a->At_val, a->r_next, a->r,
-                                               a->At_vown, (int)a->At_qv, a->part3, stopw, st,
-                                               a->At_ell_row, a->At_ell_val, a->n);
+      HalfArgs h{it, 0, guard};
+      h.own = &own;
+      h.peer = &pj;
+      // box-Schur: the kernels count own entries only, all of part1's second half.  Else the
+      // kernel folds [p1 + np1, p1 + 2 np1): hand it the own range as that window
+      const int cnt = boxp ? P.np1 : (int)(e->p1_hi[0] - e->p1_lo[0]);
+      const double *p1 = boxp ? a->part1 : a->part1 + P.np1 + e->p1_lo[0] - cnt;
+      return launch_projection_half(a, P, h, p1, cnt, &np2, &np3, &np4, st);
     }
-    // step2 + H.p with the all-reduce of the four sums and the halo exchange of g in its
-    // prologue; the own sums of p'Hp stay in part1 for the next step1
-    const int np4 = part4_count(a);
-    if (e->p4_hi > np4) return IPX_EINVAL;
-    if (!boxp && (e->p2_hi > (int)a->A_ntiles || e->p3_hi[0] > np4)) return IPX_EINVAL;
+    // the own sums of p'Hp stay in part1 for the next step1
+    if (e->p4_hi > P.np4) return IPX_EINVAL;
+    if (!boxp && (e->p2_hi > (int)a->A_ntiles || e->p3_hi[0] > P.np4)) return IPX_EINVAL;
     int rc = peer_job_geometry(e, peer, &pj);
     if (rc) return rc;
     if (++peer->seq == 0) ++peer->seq;
@@ -1646,70 +1926,19 @@ static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
     pj.hseq = peer->hseq;
     pj.pack_out = e->pack;
     ++peer->fused;
-    if (boxp)       // the kernels counted own entries only: the own sums are the whole arrays
-      return launch_step2_hp(a, it, mode, a->part2, step1_box_blocks(a), a->part3,
-                             ipx_boxschur_project_count((const ipx_boxschur_args *)a->banded),
-                             a->part4 + e->p4_lo, (int)(e->p4_hi - e->p4_lo), st, nullptr, &pj);
-    return launch_step2_hp(a, it, mode, a->part2 + e->p2_lo, (int)(e->p2_hi - e->p2_lo),
-                           a->part3 + e->p3_lo[0], (int)(e->p3_hi[0] - e->p3_lo[0]),
-                           a->part4 + e->p4_lo, (int)(e->p4_hi - e->p4_lo), st, nullptr, &pj);
+    HalfArgs h{it, mode, guard};
+    h.peer = &pj;
+    // (box-Schur: the kernels counted own entries only, the own sums are the whole arrays)
+    const int64_t lo2 = boxp ? 0 : e->p2_lo, hi2 = boxp ? P.np2 : e->p2_hi;
+    const int64_t lo3 = boxp ? 0 : e->p3_lo[0], hi3 = boxp ? P.np3 : e->p3_hi[0];
+    return launch_update_half(a, P, h, a->part2 + lo2, (int)(hi2 - lo2), a->part3 + lo3,
+                              (int)(hi3 - lo3), a->part4 + e->p4_lo, (int)(e->p4_hi - e->p4_lo), st);
   }
-  const double *guard = a->state + ST_STOP;
-  const int grid = (int)a->vec_grid;
-  int rc = IPX_OK;
   if (phase == 0) {
-    const bool fuse1 = fused_ar(a);
-    const bool boxp = box_project(a);
-    int np4 = 0, np3 = (int)a->At_ntiles, np2 = fuse1 ? (int)a->A_ntiles : grid;
-    if (boxp) {
-      // barrier problem: the projection without the box rows as matrix rows (csrc/boxschur.hip);
-      // the kernels count a rank's own entries only (element mask), so the own sums are the
-      // sums over ALL their partials
-      const ipx_boxschur_args *b = (const ipx_boxschur_args *)a->banded;
-      const OwnRanges own = own_of(e);
-      np2 = step1_box_blocks(a);
-      launch_step1_box<false>(a, b, it, e->s1, 1, np2, own, ipx_no_peer{}, st);
-      IPX_CHECK_LAUNCH();
-      int32_t n3 = 0, n4 = 0;
-      rc = ipx_boxschur_project_from(b, a->r, a->r, a->part3, &n3, a->part4, &n4, guard, 1, st, &own);
-      if (rc) return rc;
-      np3 = n3;
-      np4 = n4;
-    } else {
-      if (fuse1) {
-        rc = launch_step1_ar(a, it, e->s1, 1, st);
-        if (rc) return rc;
-      } else {
-        hipLaunchKernelGGL(k_cg_step1, dim3(ipx_xcd_grid(grid)), dim3(VB), 0, st, a->n, a->state,
-                           it & 1, e->s1, 1, a->x, a->p, a->r, a->Hp, a->lb, a->ub, a->part2, grid,
-                           own_of(e));
-        IPX_CHECK_LAUNCH();
-        ipx_csr_view A{(int)a->m, (int)a->n, a->A_rowptr, a->A_colidx, a->A_val, a->A_tiles,
-                       (int)a->A_ntiles};
-        rc = ipx_spmv_launch(A, a->r, 1.0, nullptr, 0.0, nullptr, a->w, nullptr, guard, st);
-        if (rc) return rc;
-      }
-      const double *r_in = fuse1 ? a->r_next : a->r;
-      if (a->solver_kind == 0 && a->At_vown && a->At_qv > 0) {
-        rc = ipx_banded_solve_resid_atv_launch(a->banded, a->w, a->v, a->part4, &np4,
-                                               a->At_rowptr, a->At_colidx, a->At_val, r_in, a->r,
-                                               a->At_vown, (int)a->At_qv, a->part3, guard, st,
-                                               a->At_ell_row, a->At_ell_val, a->n);
-        if (rc) return rc;
-        np3 = np4;
-      } else {
-        if (a->solver_kind == 1)    // box rows eliminated analytically, banded Schur complement
-          rc = ipx_boxschur_solve((const ipx_boxschur_args *)a->banded, a->w, a->v, a->part4,
-                                  &np4, guard, st);
-        else
-          rc = ipx_banded_solve_resid_launch(a->banded, a->w, a->v, a->part4, &np4, guard, st);
-        if (rc) return rc;
-        ipx_csr_view At{(int)a->n, (int)a->m, a->At_rowptr, a->At_colidx, a->At_val, a->At_tiles,
-                        (int)a->At_ntiles};
-        rc = ipx_spmv_launch(At, a->v, -1.0, nullptr, 1.0, r_in, a->r, a->part3, guard, st);
-        if (rc) return rc;
-      }
-    }
+    HalfArgs h{it, 0, guard};
+    h.own = &own;
+    int rc = launch_projection_half(a, P, h, e->s1, 1, &np2, &np3, &np4, st);
+    if (rc) return rc;
     if (e->p4_hi > np4 || (!boxp && e->p2_hi > np2)) return IPX_EINVAL;
     RangeJob job;
     job.npieces = (int)e->nseg;
@@ -1717,6 +1946,7 @@ static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
     for (int pc = 0; pc < 4; ++pc)
       for (int q = 0; q < 4; ++q) { job.ptr[pc][q] = a->part2; job.count[pc][q] = 0; }
     // ||x+ap||^2, #violations and ||A g||^2 are single ranges (piece 0); ||g||^2 one per segment
+    // (box-Schur projection: the kernels counted own entries only, the whole arrays)
     const int64_t p2lo = boxp ? 0 : e->p2_lo, p2hi = boxp ? np2 : e->p2_hi;
     job.ptr[0][0] = a->part2 + p2lo;        job.count[0][0] = (int)(p2hi - p2lo);
     job.ptr[0][1] = a->part2 + np2 + p2lo;  job.count[0][1] = (int)(p2hi - p2lo);
@@ -1733,18 +1963,16 @@ static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
     }
     return launch_pack(a, e, job, e->pack, true, st);       // unguarded: see pack_hp
   }
-  // phase 1
-  if (fused_hp(a)) {
-    rc = launch_step2_hp(a, it, mode, e->pack, 1, e->pack + 2, 1, e->pack + 3, 1, st);
-  } else {
-    hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid(grid)), dim3(VB), 0, st, a->n, a->state,
-                       it & 1, mode, e->pack, 1, e->pack + 2, 1, e->pack + 3, 1, a->x, a->p, a->r,
-                       grid);
-    IPX_CHECK_LAUNCH();
-    rc = launch_hp(a, guard, st);
-  }
+  const HalfArgs h{it, mode, guard};
+  int rc = launch_update_half(a, P, h, e->pack, 1, e->pack + 2, 1, e->pack + 3, 1, st);
   if (rc) return rc;
-  return pack_hp(a, e, st);
+  return pack_hp(a, e, P, st);
+}
+
+int ipx_cg_shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t phase,
+                          int32_t it, int32_t mode, void *stream) {
+  if (!a) return IPX_EINVAL;
+  return shard2_segment(a, e, plan_of(a), phase, it, mode, stream, false);
 }
 
 // Iterations [it_begin, it_end) of the sharded loop in ONE call: needs the peer mailbox
@@ -1753,15 +1981,16 @@ static int shard2_segment(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
 int ipx_cg_shard2_iterate(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t it_begin,
                           int32_t it_end, void *stream) {
   if (!a || !e || !e->peer || it_end < it_begin || a->LR_W) return IPX_EINVAL;
+  const LoopPlan P = plan_of(a);
   // e->fuse_comm is the GROUP's decision (ipx_cg_shard2_fusable on every rank, the minimum
   // taken over the ranks by the caller): the two forms order the collectives of an iteration
   // differently, so a rank may not pick one from its own slice of the matrices
   const bool fuse = e->fuse_comm != 0;
-  if (fuse && !peer_fusable(a, e)) return IPX_EINVAL;
+  if (fuse && !peer_fusable(a, e, P)) return IPX_EINVAL;
   for (int it = it_begin; it < it_end; ++it) {
-    int rc = shard2_segment(a, e, 0, it, 0, stream, fuse);
+    int rc = shard2_segment(a, e, P, 0, it, 0, stream, fuse);
     if (rc) return rc;
-    rc = shard2_segment(a, e, 1, it, 0, stream, fuse);
+    rc = shard2_segment(a, e, P, 1, it, 0, stream, fuse);
     if (rc) return rc;
   }
   return IPX_OK;
@@ -1771,20 +2000,15 @@ int ipx_cg_shard2_iterate(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t
 int ipx_cg_shard2_resident(const ipx_cg_args *a, const ipx_shard2_ext *e, int32_t it_begin,
                            int32_t it_end, void *stream) {
   if (!a || !e || a->LR_W) return IPX_EINVAL;
-  return ipx_cg_shard2_resident_launch(a, e, it_begin, it_end, part1_count(a), (hipStream_t)stream);
+  return ipx_cg_shard2_resident_launch(a, e, it_begin, it_end, plan_of(a).np1, (hipStream_t)stream);
 }
 
-// p at the row-tile boundaries of H (the fused step2 + H.p kernel reads its neighbours' OLD p
-// there) from the current a->p
+// p at the row-tile boundaries of H from the current a->p, where the fused step2 + H.p kernel
+// is enabled (launch_save_pb)
 int ipx_cg_save_pb(const ipx_cg_args *a, void *stream) {
   if (!a) return IPX_EINVAL;
-  if (!fused_hp(a)) return IPX_OK;
-  const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
-  hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0,
-                     (hipStream_t)stream, a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb,
-                     xsums_tag(a));
-  IPX_CHECK_LAUNCH();
-  return IPX_OK;
+  if (!plan_of(a).fused_hp) return IPX_OK;
+  return launch_save_pb(a, (hipStream_t)stream);
 }
 
 // 1 when THIS rank's argument block allows the collectives in the prologues of the loop's own
@@ -1795,13 +2019,13 @@ int ipx_cg_shard2_fusable(const ipx_cg_args *a, const ipx_shard2_ext *e) {
   if (!a || !e || !e->peer || a->LR_W) return 0;
   ipx_shard2_ext asked = *e;
   asked.fuse_comm = 1;
-  return peer_fusable(a, &asked) ? 1 : 0;
+  return peer_fusable(a, &asked, plan_of(a)) ? 1 : 0;
 }
 
 // The own-range sum of the p'Hp partials on its own (priming the sharded loop).
 int ipx_cg_shard2_fold_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, void *stream) {
   if (!a || !e || !e->s1 || e->nseg < 1 || e->nseg > 4 || a->LR_W) return IPX_EINVAL;
-  return pack_hp(a, e, (hipStream_t)stream);
+  return pack_hp(a, e, plan_of(a), (hipStream_t)stream);
 }
 
 // The state block of a new call written ON THE DEVICE from reductions its priming left in
@@ -1978,8 +2202,6 @@ int ipx_cg_prime_state(double *state, const double *red, const int32_t *idx7, do
 // a time (ipsolver/projector.py null_space_enqueue), ~25 calls and three copies.  CSR A and H
 // (+ optional diagonal), banded or box-Schur solver; red: >= 14 doubles of device memory, ws:
 // the reduction workspace (IPX_WS_DOUBLES).
-static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hipStream_t st,
-                      hipEvent_t *ev);
 static int prime_solve(const ipx_cg_args *a, const double *w, double *v, void *stream) {
   if (a->solver_kind == 1)
     return ipx_boxschur_solve((const ipx_boxschur_args *)a->banded, w, v, nullptr, nullptr, nullptr,
@@ -2028,9 +2250,6 @@ static int prime_project(const ipx_cg_args *a, const ipx_csr_view &A, const ipx_
 // of ||z||^2 (pz) and of ||w - (A A') v||^2 = ||A z||^2 (pt: the orthogonality measure the
 // loop's iterations use, projections.py:52 without a second product by A) -- two launches
 // instead of four.  guard: *guard != 0 skips both (a correction step that is not due).
-static bool prime_has_tail(const ipx_cg_args *a) {
-  return a->solver_kind == 0 && a->At_vown && a->At_qv > 0;
-}
 static int prime_project_tail(const ipx_cg_args *a, const ipx_csr_view &A, const double *x,
                               double *z, double *pz, double *pt, int *np, double sign,
                               const double *guard, hipStream_t st) {
@@ -2043,10 +2262,10 @@ static int prime_project_tail(const ipx_cg_args *a, const ipx_csr_view &A, const
 }
 
 // either way, the partials registered for the state kernel's fold
-static int prime_project_any(const ipx_cg_args *a, const ipx_csr_view &A, const ipx_csr_view &At,
-                             const double *x, double *z, PrimeRed &R, int base, bool have_xnorm,
-                             double sign, hipStream_t st) {
-  if (!prime_has_tail(a)) return prime_project(a, A, At, x, z, R, base, have_xnorm, sign, st);
+static int prime_project_any(const ipx_cg_args *a, const LoopPlan &P, const ipx_csr_view &A,
+                             const ipx_csr_view &At, const double *x, double *z, PrimeRed &R,
+                             int base, bool have_xnorm, double sign, hipStream_t st) {
+  if (P.proj != PJ_SOLVE_TAIL) return prime_project(a, A, At, x, z, R, base, have_xnorm, sign, st);
   int rc = have_xnorm ? IPX_OK : ipx_norms(a->n, x, R.red + base + 4, R.ws + R.off, st);
   if (rc) return rc;
   const int cap = (int)((a->m + 255) / 256) + 8;
@@ -2066,8 +2285,8 @@ static int prime_project_any(const ipx_cg_args *a, const ipx_csr_view &A, const 
 // before this one, whose step this decide kernel folds first).  z - A'v' with v' = (A A')^-1 A z
 // is the same expression for z and for -z (every launch an odd function of its input, bit for
 // bit), so the negated second projection needs no sign.
-static int prime_project_stepped(const ipx_cg_args *a, const ipx_csr_view &A,
-                                 const ipx_csr_view &At, const double *x, double *z, PrimeRed &R,
+static int prime_project_stepped(const ipx_cg_args *a, const LoopPlan &P,
+                                 const ipx_csr_view &A, const ipx_csr_view &At, const double *x, double *z, PrimeRed &R,
                                  int base, int xslot, int pj, bool have_xnorm, double sign,
                                  double orth_tol, double norm_A, const double *norm_A2_dev,
                                  double canc2, const PrimeStep *prev, PrimeStep *step,
@@ -2075,7 +2294,7 @@ static int prime_project_stepped(const ipx_cg_args *a, const ipx_csr_view &A,
   const int n0 = R.f.n;
   int rc;
   const double *skip = R.red + PR_SKIP + pj;
-  if (prime_has_tail(a)) {
+  if (P.proj == PJ_SOLVE_TAIL) {
     if (!have_xnorm) {
       rc = ipx_norms(a->n, x, R.red + base + 4, R.ws + R.off, st);
       if (rc) return rc;
@@ -2152,6 +2371,7 @@ int ipx_cg_prime_dev(const ipx_cg_args *a, const int32_t *A_tiles, int32_t A_nti
       !a->H_rowptr || !a->t || first_end < 0 || a->LR_W)   // (H x0 would miss a low-rank term)
     return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  const LoopPlan P = plan_of(a);
   const ipx_csr_view A{(int)a->m, (int)a->n, a->A_rowptr, a->A_colidx, a->A_val, A_tiles, A_ntiles};
   const ipx_csr_view At{(int)a->n, (int)a->m, a->At_rowptr, a->At_colidx, a->At_val, a->At_tiles,
                         (int)a->At_ntiles};
@@ -2189,16 +2409,16 @@ int ipx_cg_prime_dev(const ipx_cg_args *a, const int32_t *A_tiles, int32_t A_nti
       PrimeFolds &f = R.f;
       f.part[f.n] = c_part; f.count[f.n] = c_npart; f.slot[f.n] = 4; f.single[f.n] = 0; ++f.n;
     }
-    rc = prime_project_any(a, A, At, t, a->r, R, 0, b != nullptr || c_known, 1.0, st);
+    rc = prime_project_any(a, P, A, At, t, a->r, R, 0, b != nullptr || c_known, 1.0, st);
     if (rc) return rc;
-    rc = prime_project_any(a, A, At, a->r, a->p, R, 6, true, -1.0, st);
+    rc = prime_project_any(a, P, A, At, a->r, a->p, R, 6, true, -1.0, st);
     if (rc) return rc;
   } else {
-    rc = prime_project_stepped(a, A, At, t, a->r, R, 0, 4, 0, false, 1.0, orth_tol, norm_A,
+    rc = prime_project_stepped(a, P, A, At, t, a->r, R, 0, 4, 0, false, 1.0, orth_tol, norm_A,
                                norm_A2_dev, canc2, nullptr, &s1, st);
     if (rc) return rc;
     // g0 = Z r0 lands in p as -g0 (the first direction); its input norm ||r0||^2 is red[0]
-    rc = prime_project_stepped(a, A, At, a->r, a->p, R, 6, 0, 1, true, -1.0, orth_tol, norm_A,
+    rc = prime_project_stepped(a, P, A, At, a->r, a->p, R, 6, 0, 1, true, -1.0, orth_tol, norm_A,
                                norm_A2_dev, canc2, &s1, &s2, st);
     if (rc) return rc;
   }
@@ -2209,10 +2429,10 @@ int ipx_cg_prime_dev(const ipx_cg_args *a, const int32_t *A_tiles, int32_t A_nti
                      ix, tol_in, radius, orth_tol, norm_A, canc2, radius_dev, norm_A2_dev, s2,
                      (b || !steps) ? 0 : 1);
   IPX_CHECK_LAUNCH();
-  rc = launch_hp(a, nullptr, st);
+  rc = launch_hp(a, P, nullptr, st);
   if (rc || first_end == 0) return rc;
   // the call's first batch behind the same entry (stop code 9: its launches do nothing)
-  return cg_iterate(a, 0, first_end, st, nullptr);
+  return cg_iterate(a, P, 0, first_end, st, nullptr);
 }
 
 extern "C" {
@@ -2221,59 +2441,38 @@ extern "C" {
 // the host to prime the loop).
 int ipx_cg_hp(const ipx_cg_args *a, void *stream) {
   if (!a) return IPX_EINVAL;
-  return launch_hp(a, nullptr, (hipStream_t)stream);
+  return launch_hp(a, plan_of(a), nullptr, (hipStream_t)stream);
 }
 
-// The fused step2 + H.p kernel on its own (iteration `it`, step2 mode bits as
-// in ipx_cg_resume); IPX_EINVAL when the argument block does not enable it.
+// The update half with the fused step2 + H.p kernel on its own (iteration `it`, step2 mode bits
+// as in ipx_cg_resume), long partial arrays compacted first as in the loop; IPX_EINVAL when the
+// argument block does not enable the kernel.
 int ipx_cg_step2_hp(const ipx_cg_args *a, int32_t it, int32_t mode, void *stream) {
-  if (!a || !fused_hp(a) || (mode & ~3)) return IPX_EINVAL;   // (bit 4: ipx_cg_iterate's alone)
-  hipStream_t st = (hipStream_t)stream;
-  // long partial arrays are compacted first, as in the loop (cg_iterate): every workgroup folds
-  // all of them, and at n = 1.6e7 the 6000 uncompacted ||g||^2 partials doubled what a
-  // workgroup reads -- bench.py's "dominant kernel on its own" measured 495 us where the same
-  // kernel takes 226 us inside the loop
-  const double *p2 = a->part2, *p3 = a->part3, *p4 = a->part4;
-  int np2 = part2_count(a), np3 = part3_count(a), np4 = part4_count(a);
-  Compactor cmp(a);
-  if (!(mode & 1)) cmp.add(p2, np2, 2, 1024);
-  cmp.add(p3, np3, 2, 2048);
-  if (!(mode & 2)) cmp.add(p4, np4, 1, 1024);
-  int rc = cmp.launch(nullptr, st);
-  if (rc) return rc;
-  rc = launch_step2_hp(a, it, mode, p2, np2, p3, np3, p4, np4, st);
-  if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, a->state + ST_STOP, st);
-  return rc;
+  if (!a || (mode & ~3)) return IPX_EINVAL;                   // (bit 4: ipx_cg_iterate's alone)
+  LoopPlan P = plan_of(a);
+  if (!P.fused_hp) return IPX_EINVAL;
+  P.step2 = S2_FUSED_HP;
+  Compactor cmp(a, nullptr);
+  HalfArgs h{it, mode, a->state + ST_STOP};
+  h.cmp = &cmp;
+  return launch_update_half(a, P, h, a->part2, P.np2, a->part3, P.np3, a->part4, P.np4,
+                            (hipStream_t)stream);
 }
 
-// Tail of an iteration after the host handled a stop-5 / stop-6 event:
-// step2 with the given mode, then Hp = H p.
+// Tail of an iteration after the host handled a stop-5 / stop-6 event: the update half with
+// the given mode and step2 as the vector kernel, then Hp = H p.
 int ipx_cg_resume(const ipx_cg_args *a, int32_t it, int32_t mode, void *stream) {
   if (!a) return IPX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const double *guard = a->state + ST_STOP;
-  int np3, np4;
-  if (dense_loop(a)) {                        // workgroups of the dense matvecs (rows / 4, capped)
-    np3 = (int)std::min<int64_t>((a->n + 3) / 4, 2048);
-    np4 = (int)std::min<int64_t>((a->m + 3) / 4, 2048);
-  } else {
-    np3 = part3_count(a);
-    np4 = part4_count(a);
-  }
-  hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
-                     a->state, it & 1, mode, a->part2, part2_count(a), a->part3, np3, a->part4,
-                     np4, a->x, a->p, a->r, (int)a->vec_grid);
-  IPX_CHECK_LAUNCH();
-  return launch_hp(a, guard, st);
+  LoopPlan P = plan_of(a);
+  P.step2 = S2_VECTOR;
+  const HalfArgs h{it, mode, a->state + ST_STOP};
+  return launch_update_half(a, P, h, a->part2, P.np2, a->part3, P.np3, a->part4, P.np4,
+                            (hipStream_t)stream);
 }
-
-// Enqueue iterations it_begin .. it_end-1.  Never synchronises.
-static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hipStream_t st,
-                      hipEvent_t *ev);
 
 int ipx_cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, void *stream) {
   if (!a || it_end < it_begin) return IPX_EINVAL;
-  return cg_iterate(a, it_begin, it_end, (hipStream_t)stream, nullptr);
+  return cg_iterate(a, plan_of(a), it_begin, it_end, (hipStream_t)stream, nullptr);
 }
 
 // Instrumented variant for bench.py: HIP events are recorded on `stream`
@@ -2287,6 +2486,7 @@ int ipx_cg_iterate_timed(const ipx_cg_args *a, int32_t it_begin, int32_t it_end,
                          void *stream) {
   if (!a || it_end < it_begin || !ms_out) return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  const LoopPlan P = plan_of(a);
   const int per_it = IPX_CG_NCLASS + 1;
   const int nit = it_end - it_begin;
   std::vector<hipEvent_t> ev((size_t)nit * per_it);
@@ -2294,7 +2494,7 @@ int ipx_cg_iterate_timed(const ipx_cg_args *a, int32_t it_begin, int32_t it_end,
     if (hipEventCreate(&e) != hipSuccess) return IPX_ELAUNCH;
   int rc = IPX_OK;
   for (int i = 0; i < nit && rc == IPX_OK; ++i)
-    rc = cg_iterate(a, it_begin + i, it_begin + i + 1, st, ev.data() + (size_t)i * per_it);
+    rc = cg_iterate(a, P, it_begin + i, it_begin + i + 1, st, ev.data() + (size_t)i * per_it);
   if (hipStreamSynchronize(st) != hipSuccess) rc = IPX_ELAUNCH;
   for (int c = 0; c < IPX_CG_NCLASS; ++c) ms_out[c] = 0.f;
   if (rc == IPX_OK) {
@@ -2307,196 +2507,6 @@ int ipx_cg_iterate_timed(const ipx_cg_args *a, int32_t it_begin, int32_t it_end,
   }
   for (auto &e : ev) (void)hipEventDestroy(e);
   return rc;
-}
-
-// Dense Jacobian (BASELINE config 2; solver_kind 2): the same state machine over the dense
-// matvecs of csrc/dense.hip, whose epilogues carry the reductions.  A (m x n) and A' (n x m)
-// row major in A_val / At_val, `banded` = G^-1 (M x M, M = m rounded up to 32; w and v are M
-// long with a zero tail), H dense (H_rowptr NULL) or CSR.  Seven launches per iteration:
-// step1, w = A r, v = G^-1 w, g = r - A'v, t = A g (the reference's orthogonality measure,
-// projections.py:52, literally), step2, Hp = H p.
-static int cg_iterate_dense(const ipx_cg_args *a, int32_t it_begin, int32_t it_end,
-                            hipStream_t st) {
-  const double *guard = a->state + ST_STOP;
-  const int n = (int)a->n, m = (int)a->m;
-  const int M = ((m + 31) / 32) * 32;
-  const int grid = (int)a->vec_grid;
-  const double *Ginv = (const double *)a->banded;
-  for (int it = it_begin; it < it_end; ++it) {
-    hipLaunchKernelGGL(k_cg_step1, dim3(ipx_xcd_grid(grid)), dim3(VB), 0, st, a->n, a->state,
-                       it & 1, a->part1, part1_count(a), a->x, a->p, a->r, a->Hp, a->lb, a->ub,
-                       a->part2, grid, own_all(a->n));
-    IPX_CHECK_LAUNCH();
-    int np = 0, np3 = 0, np4 = 0;
-    int rc = ipx_dense_gemv_launch(m, n, a->A_val, n, a->r, 1.0, nullptr, 0.0, nullptr, a->w,
-                                   nullptr, &np, guard, st);
-    if (rc) return rc;
-    rc = ipx_dense_gemv_launch(M, M, Ginv, M, a->w, 1.0, nullptr, 0.0, nullptr, a->v, nullptr, &np,
-                               guard, st);
-    if (rc) return rc;
-    rc = ipx_dense_gemv_launch(n, m, a->At_val, m, a->v, -1.0, nullptr, 1.0, a->r, a->r, a->part3,
-                               &np3, guard, st);                      // g = r - A'v, ||g||^2
-    if (rc) return rc;
-    rc = ipx_dense_gemv_launch(m, n, a->A_val, n, a->r, 1.0, nullptr, 0.0, nullptr, a->t, a->part4,
-                               &np4, guard, st);                      // ||A g||^2
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid(grid)), dim3(VB), 0, st, a->n, a->state,
-                       it & 1, 0, a->part2, grid, a->part3, np3, a->part4, np4, a->x, a->p, a->r,
-                       grid);
-    IPX_CHECK_LAUNCH();
-    rc = launch_hp(a, guard, st);
-    if (rc) return rc;
-  }
-  return IPX_OK;
-}
-
-static int cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, hipStream_t st,
-                      hipEvent_t *ev) {
-  if (dense_loop(a)) return ev ? IPX_EINVAL : cg_iterate_dense(a, it_begin, it_end, st);
-  if (!ev && it_end > it_begin && ipx_cg_resident_ok(a)) {
-    // small banded problems (one CU per workgroup of the solve): the whole batch as ONE
-    // resident launch (csrc/resident.hip), which leaves x, p, r, Hp, the state block and the
-    // partial arrays as these launches would -- the tile boundaries of p for the fused step2 +
-    // H.p kernel (an event handler's resume, a later batch on the separate launches) follow it
-    int rc = ipx_cg_resident_launch(a, it_begin, it_end, part1_count(a), part2_count(a),
-                                    part3_count(a), part4_count(a), st);
-    if (rc) return rc;
-    if (fused_hp(a)) {
-      const int tot = (int)(a->H_ntiles * 2 * a->H_hmax);
-      hipLaunchKernelGGL(k_cg_save_pb, dim3((tot + IPX_BLOCK - 1) / IPX_BLOCK), dim3(IPX_BLOCK), 0,
-                         st, a->p, a->H_tiles, (int)a->H_ntiles, (int)a->H_hmax, a->pb,
-                         xsums_tag(a));
-      IPX_CHECK_LAUNCH();
-    }
-    return IPX_OK;
-  }
-  const double *guard = a->state + ST_STOP;
-  ipx_csr_view A{(int)a->m, (int)a->n, a->A_rowptr, a->A_colidx, a->A_val, a->A_tiles, (int)a->A_ntiles};
-  ipx_csr_view At{(int)a->n, (int)a->m, a->At_rowptr, a->At_colidx, a->At_val, a->At_tiles, (int)a->At_ntiles};
-#define MARK(i) do { if (ev) (void)hipEventRecord(ev[i], st); } while (0)
-  int np4 = 1;
-  // a batch whose fused step2 + H.p launches run without the carried sums (trust radius +inf)
-  // changes x and p and leaves none: their tag is void from here on (one launch per batch)
-  if (a->xsums && !xsums_on(a) && it_end > it_begin) {
-    hipLaunchKernelGGL(k_xsums_void, dim3(1), dim3(1), 0, st, xsums_tag(a));
-    IPX_CHECK_LAUNCH();
-  }
-  for (int it = it_begin; it < it_end; ++it) {
-    MARK(0);
-    int rc, np3 = (int)a->At_ntiles;
-    const bool fuse1 = fused_ar(a);
-    const double *r_in = fuse1 ? a->r_next : a->r;      // what the r - A'v SpMV reads
-    Compactor cmp(a);
-    const double *p1 = a->part1;
-    int np1 = part1_count(a);
-    cmp.add(p1, np1, 2, 2048);      // beyond what a consumer folds in one or two rounds
-    // trust radius +inf, no box (fused step1 implies no box): the radius / box tests of
-    // qp_subproblem.py:583,599 cannot trigger; their sums are neither formed nor folded
-    const bool no_xn2 = fuse1 && a->no_radius != 0;
-    // a finite radius: the test is formed from the sums the previous iteration's fused step2 +
-    // H.p kernel left (ipx_cg_args.xsums) -- inside a batch, or where the caller vouches for
-    // the batch before; the fused step1 then reads neither x nor p.  The first iteration of a
-    // call reads them as before.
-    const bool xs_on = xsums_on(a);
-    const bool carried = xs_on && (it > it_begin || a->xsums_carry != 0);
-    rc = cmp.launch(guard, st);
-    if (rc) return rc;
-    if (fuse1) {
-      MARK(1);
-      // r_next = r + alpha Hp;  w = A r_next
-      rc = launch_step1_ar(a, it, p1, np1, st, no_xn2, nullptr, carried);
-      if (rc) return rc;
-      MARK(2);
-    } else if (a->m > 0 && box_project(a)) {
-      const ipx_boxschur_args *b = (const ipx_boxschur_args *)a->banded;
-      const int nblk = step1_box_blocks(a);
-      launch_step1_box<false>(a, b, it, p1, np1, nblk, own_all(a->n), ipx_no_peer{}, st);
-      IPX_CHECK_LAUNCH();
-      MARK(1);
-    } else {
-      hipLaunchKernelGGL(k_cg_step1, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
-                         a->state, it & 1, p1, np1, a->x, a->p, a->r,
-                         a->Hp, a->lb, a->ub, a->part2, (int)a->vec_grid, own_all(a->n));
-      IPX_CHECK_LAUNCH();
-      MARK(1);
-    }
-    if (a->m > 0 && box_project(a)) {
-      // simple (box) rows eliminated analytically and never multiplied as matrix rows:
-      // g = r - A'(A A')^-1 A r in one call (csrc/boxschur.hip ipx_boxschur_project)
-      int32_t n3 = 0, n4 = 0;
-      rc = ipx_boxschur_project_from((const ipx_boxschur_args *)a->banded, a->r, a->r, a->part3,
-                                     &n3, a->part4, &n4, guard, 1, st);
-      if (rc) return rc;
-      np3 = n3;
-      np4 = n4;
-      MARK(2); MARK(3); MARK(4); MARK(5);
-    } else if (a->m > 0) {
-      if (!fuse1) {
-        // w = A r_next
-        rc = ipx_spmv_launch(A, a->r, 1.0, nullptr, 0.0, nullptr, a->w, nullptr, guard, st);
-        if (rc) return rc;
-        MARK(2);
-      }
-      // v = (AA')^-1 w, and ||A g||^2 for the orthogonality test as the
-      // constraint-space residual ||w - (A A') v||^2 from the same launch
-      // (see k_correct_oop / k_band_residual); part4 holds ceil(m/256) doubles
-      np3 = (int)a->At_ntiles;
-      if (a->solver_kind == 0 && a->At_vown && a->At_qv > 0) {
-        // decoupled banded solve with g = r - A'v as its tail (one launch for both);
-        // ||g||^2 partials are then per workgroup of that kernel
-        rc = ipx_banded_solve_resid_atv_launch(a->banded, a->w, a->v, a->part4, &np4,
-                                               a->At_rowptr, a->At_colidx, a->At_val, r_in, a->r,
-                                               a->At_vown, (int)a->At_qv, a->part3, guard, st,
-                                               a->At_ell_row, a->At_ell_val, a->n);
-        if (rc) return rc;
-        np3 = np4;
-        MARK(3);
-        MARK(4);
-      } else {
-        if (a->solver_kind == 1)
-          rc = ipx_boxschur_solve((const ipx_boxschur_args *)a->banded, a->w, a->v, a->part4,
-                                  &np4, guard, st);
-        else
-          rc = ipx_banded_solve_resid_launch(a->banded, a->w, a->v, a->part4, &np4, guard, st);
-        if (rc) return rc;
-        MARK(3);
-        // r = r - A'v  (g_next), partials of ||g||^2
-        rc = ipx_spmv_launch(At, a->v, -1.0, nullptr, 1.0, r_in, a->r, a->part3, guard, st);
-        if (rc) return rc;
-        MARK(4);
-      }
-      MARK(5);
-    }
-    const double *p2 = a->part2, *p3 = a->part3, *p4 = a->part4;
-    int np2 = part2_count(a), n4 = np4;
-    // (carried: the folded sums in part2's place)
-    const double *xin = carried ? a->xsums + 3 * a->H_ntiles + 1 : nullptr;
-    if (!no_xn2 && !carried) cmp.add(p2, np2, 2, 1024);
-    if (a->m > 0) {
-      cmp.add(p3, np3, 2, 2048);
-      cmp.add(p4, n4, 1, 1024);
-    }
-    rc = cmp.launch(guard, st);
-    if (rc) return rc;
-    if (fused_hp(a)) {
-      MARK(6);
-      const ipx_xsums_job xs{a->xsums, xin, it, xs_on ? 1 : 0};
-      rc = launch_step2_hp(a, it, (a->m > 0 ? 0 : 2) | (no_xn2 ? 1 : 0) | (carried ? 4 : 0), p2, np2,
-                           p3, np3, p4, n4, st, a->r, nullptr, &xs);
-      if (!rc && lowrank_on(a)) rc = launch_lowrank(a, true, guard, st);
-    } else {
-      hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
-                         a->state, it & 1, (a->m > 0 ? 0 : 2) | (no_xn2 ? 1 : 0), p2, np2, p3, np3,
-                         p4, n4, a->x, a->p, a->r, (int)a->vec_grid);
-      IPX_CHECK_LAUNCH();
-      MARK(6);
-      rc = launch_hp(a, guard, st);
-    }
-    if (rc) return rc;
-    MARK(7);
-  }
-#undef MARK
-  return IPX_OK;
 }
 
 }  // extern "C"
