@@ -398,6 +398,23 @@ typedef struct ipx_cg_args {
    * stand-alone ipx_cg_step2_hp runs the kernel without the sums and leaves the tag alone: do
    * not set xsums_carry behind it. */
   double *xsums;
+  /* The projection half of an iteration as ONE launch (csrc/banded.hip k_step1_solve_tail:
+   * step1, w = A r_next, the cyclic-reduction solve and g = r_next - A'v on the solve's windows;
+   * two launches per iteration).  fused_proj != 0 asks for it; the library takes it when the
+   * fused step1, the solve's tail in its ELL(2) form and the window tables above (A_off16's
+   * siblings A_rowfirst, A_rl <= 16, P_win, P_nspan <= 4096) are all bound, n is even, no box,
+   * and a resident launch does not apply -- else the three launches, whose tables stay bound.
+   * A_ell_val / A_ell_off16 = A once more, ELL-transposed for one lane per row: entry k of row
+   * i at [k * m + i], the values and the column as a 16-bit offset from A_rowfirst[i].
+   * r_where = one int32 of device memory, zeroed once: within a batch the roles of r and r_next
+   * alternate (a workgroup's g must not overwrite entries of r its neighbours' windows still
+   * read), the word says where the current r lives and every entry point that enqueues
+   * iterations ends with one guarded launch that copies it back.  When an entry point returns,
+   * r holds the current residual whatever the iteration count or stop code. */
+  int64_t fused_proj;
+  const double *A_ell_val;
+  const void *A_ell_off16;
+  int32_t *r_where;
   /* != 0: the first iteration of the next ipx_cg_iterate call may take the carried sums too
    * -- the caller knows that the previous batch on this block ended exactly there without a
    * stop and that nothing has run on it since.  0: that iteration reads x and p. */

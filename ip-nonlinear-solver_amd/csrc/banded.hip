@@ -1515,6 +1515,39 @@ k_pcr_check(int m, int rows_wg, const double *__restrict__ band, int *flags) {
   }
 }
 
+// The L reduction levels of the solve kernels on one window (k_solve_pcr, k_step1_solve_tail):
+// lane t carries window rows t + k TB in a / b / d; the two LDS buffers alternate by level, their
+// identity padding (PAD rows either side) is the caller's.
+template <int NR, int TB, int RS>
+__device__ __forceinline__ void pcr_levels(int L, int R, int tid, double (&a)[NR], double (&b)[NR],
+                                           double (&d)[NR], double (&pa)[2][RS],
+                                           double (&pr)[2][RS], double (&pd)[2][RS]) {
+  constexpr int PAD = 1 << PCR_LMAX;
+  for (int s = 0; s < L; ++s) {
+    const int h = 1 << s, cur = s & 1;
+    double rc[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int r = tid + k * TB;
+      rc[k] = pcr_rcp(b[k]);
+      if (r < R) { pa[cur][PAD + r] = a[k]; pr[cur][PAD + r] = rc[k]; pd[cur][PAD + r] = d[k]; }
+    }
+    ipx_lds_barrier();
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const int r = PAD + min(tid + k * TB, R - 1);
+      const double alo = pa[cur][r - h], rlo = pr[cur][r - h], dlo = pd[cur][r - h];
+      const double ahi = pa[cur][r + h], rhi = pr[cur][r + h], dhi = pd[cur][r + h];
+      const double al = -a[k] * rlo, ga = -ahi * rhi;
+      double bn = __builtin_fma(al, a[k], b[k]);
+      bn = __builtin_fma(ga, ahi, bn);
+      double dn = __builtin_fma(al, dlo, d[k]);
+      dn = __builtin_fma(ga, dhi, dn);
+      a[k] = al * alo; b[k] = bn; d[k] = dn;
+    }
+  }
+}
+
 // TB lanes per workgroup: 512 (PCR_TB) -- measured against 256 and 1024 at n = 1e6 / 4e6: the
 // solve with its tail 10.4 / 28.8 us against 10.8 / 29.9 (256) and 12.6 / 38.6 (1024: one
 // workgroup per CU); the form that builds its own right-hand side (config 5) 7.9 us against
@@ -1667,29 +1700,7 @@ k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
     for (int u = 0; u < 2; ++u) { pa[u][r] = 0.0; pr[u][r] = 1.0; pd[u][r] = 0.0; }
   }
   // (a of the row just past the window's end is its coupling into the window: cut too)
-  for (int s = 0; s < L; ++s) {
-    const int h = 1 << s, cur = s & 1;
-    double rc[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int r = tid + k * TB;
-      rc[k] = pcr_rcp(b[k]);
-      if (r < R) { pa[cur][PAD + r] = a[k]; pr[cur][PAD + r] = rc[k]; pd[cur][PAD + r] = d[k]; }
-    }
-    ipx_lds_barrier();
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int r = PAD + min(tid + k * TB, R - 1);
-      const double alo = pa[cur][r - h], rlo = pr[cur][r - h], dlo = pd[cur][r - h];
-      const double ahi = pa[cur][r + h], rhi = pr[cur][r + h], dhi = pd[cur][r + h];
-      const double al = -a[k] * rlo, ga = -ahi * rhi;
-      double bn = __builtin_fma(al, a[k], b[k]);
-      bn = __builtin_fma(ga, ahi, bn);
-      double dn = __builtin_fma(al, dlo, d[k]);
-      dn = __builtin_fma(ga, dhi, dn);
-      a[k] = al * alo; b[k] = bn; d[k] = dn;
-    }
-  }
+  pcr_levels<NR, TB>(L, R, tid, a, b, d, pa, pr, pd);
   IPX_STAMP(3);
   // ---- x = d / b; own rows to memory, the window to LDS for the tail / residual
 #pragma unroll
@@ -1906,6 +1917,290 @@ int launch_solve_pcr(const LevDev &lv, int L, const double *w, double *x, double
   if (per <= 8) return launch_solve_pcr_q<8>(lv, L, w, x, partial, npartial, guard, *atv, st);
   return IPX_EINVAL;
 }
+
+// ---- step1, w = A r_next, the solve and g = r_next - A'v in ONE launch ------------------------
+// The boundary between k_cg_step1_ar (csrc/cg.hip) and k_solve_pcr has no global reduction across
+// it: alpha follows from the p'Hp partials every workgroup can fold itself, w is needed on the
+// solve's own window only and r_next afterwards on the workgroup's own variables only.  So a
+// workgroup of the solve forms r_next = r + alpha Hp on the column span of its window (LDS),
+// the row sums of A on the window's rows (one lane per row, entries out of an ELL-transposed
+// copy of A: coalesced) and goes on as k_solve_pcr<QV, 1, false, PCR_TB> does: same grid, same
+// windows, same vown ownership, same arithmetic (1.5 x the products of A, no r_next and no w
+// round trip through memory, one launch less).  Every sum is formed in the order of the launches
+// it replaces: the p'Hp fold by the first 256 lanes as ipx_fold_regs<1, 6> does it in a
+// workgroup of IPX_BLOCK, the row sums left to right, part3 / part4 by k_solve_pcr's lane-to-
+// variable mapping -- the same bits.  g goes to a buffer that is not r_in (a neighbour's window
+// still reads the entries this workgroup owns).
+// XN as in k_cg_step1_ar: 0 partials of ||x + alpha p||^2 over the own variables (one per
+// workgroup); 1 not formed; 2 the first `ncomp` workgroups fold a slice of the carried sums.
+// PRIME: the projection alone, for the priming (csrc/cg.hip prime_project_tail): no step -- the
+// span holds r_in itself, no p'Hp fold, no state words read or written, *guard != 0 skips the
+// launch --, g = sign (r_in - A'v) as AtvJob's sign forms it.
+template <int QV, int XN, bool PRIME = false>
+__global__ void __launch_bounds__(PCR_TB)
+k_step1_solve_tail(int m, int rows_wg, int L, const double *__restrict__ band,
+                   ipx_fused_proj_job J) {
+  constexpr int TB = PCR_TB;
+  constexpr int PAD = 1 << PCR_LMAX;
+  constexpr int RS = PCR_RMAX + 2 * PAD;
+  constexpr int QSP = IPX_FP_SPAN / TB;              // span columns per lane
+  constexpr int RLA = IPX_FP_ROW;
+  constexpr int FW = IPX_BLOCK, FU = 6;              // the p'Hp fold: lanes, loads per lane
+  constexpr int QP = (QV + 1) / 2;
+  __shared__ double pa[2][RS], pr[2][RS], pd[2][RS];
+  __shared__ double sx[PCR_RMAX];
+  __shared__ double span[IPX_FP_SPAN];
+  __shared__ double red_lds[TB / IPX_WAVE];
+  __shared__ double fold_lds[FW / IPX_WAVE];
+  const int tid = threadIdx.x, wg = blockIdx.x;
+  const int av0 = J.vown[wg], avn = J.vown[wg + 1] - av0;
+  const int c_lo = J.win[2 * wg], nspan = J.win[2 * wg + 1] - c_lo;
+  static_assert(!PRIME || XN == 1, "the priming's projection forms no radius test");
+  double stop, rtg = 0.0, tol = 0.0;
+  if constexpr (PRIME) {
+    stop = J.guard ? *J.guard : 0.0;
+  } else {
+    stop = J.st[ST_STOP];
+    rtg = J.st[J.parity ? ST_RTG1 : ST_RTG0];
+    tol = J.st[ST_TOL];
+  }
+  // p'Hp partials: the loads of ipx_fold_regs<1, FU>::load in a workgroup of FW lanes
+  double ft[FU];
+  if (!PRIME && tid < FW) {
+#pragma unroll
+    for (int u = 0; u < FU; ++u) {
+      const int i = tid + u * FW;
+      const double ld = J.p1[max(min(i, J.np1 - 1), 0)];
+      ft[u] = i < J.np1 ? ld : 0.0;
+    }
+  }
+  const int H = 1 << L;
+  const int R = rows_wg + 2 * H;
+  const int64_t g0 = (int64_t)wg * rows_wg - H;      // global row of window row 0
+  // r and H p over the span
+  double sr[QSP], sh[QSP];
+#pragma unroll
+  for (int k = 0; k < QSP; ++k) {
+    const int64_t col = min((int64_t)c_lo + max(min(tid + k * TB, nspan - 1), 0), J.n - 1);
+    sr[k] = J.r_in[col];
+    sh[k] = PRIME ? 0.0 : J.Hp[col];
+  }
+  // window row tid: its entries of A, its band entries
+  const int64_t grow = g0 + tid;
+  const bool row_in = tid < R && grow >= 0 && grow < m;
+  const int64_t gc = min(max(grow, (int64_t)0), (int64_t)m - 1);
+  const int first = J.A_rowfirst[gc] - c_lo;
+  double av[RLA];
+  int ao[RLA];
+#pragma unroll
+  for (int k = 0; k < RLA; ++k) {
+    av[k] = 0.0; ao[k] = 0;
+    if (k < J.rl) {                                   // (uniform)
+      av[k] = J.A_ell_val[(int64_t)k * m + gc];
+      ao[k] = (int)J.A_ell_off16[(int64_t)k * m + gc];
+    }
+  }
+  double a[1], b[1], d[1];
+  {
+    const double bv = band[gc], avv = band[(int64_t)m + gc];
+    a[0] = (row_in && grow >= 1 && tid >= 1) ? avv : 0.0;      // (row 0 of the window: cut)
+    b[0] = row_in ? bv : 1.0;
+  }
+  // XN = 2: this workgroup's slice of the carried sums' raw partials (k_cg_step1_ar's)
+  double xq[3] = {0.0, 0.0, 0.0}, xtag = 0.0;
+  const bool folds = XN == 2 && wg < J.ncomp && tid < IPX_XS_SLICE;
+  if (folds) {
+    const int i = wg * IPX_XS_SLICE + tid;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const double ld = J.xs_raw[q * J.nraw + min(i, J.nraw - 1)];
+      xq[q] = i < J.nraw ? ld : 0.0;
+    }
+    xtag = J.xs_raw[3 * J.nraw];
+  }
+  const bool lead = wg == 0 && tid == 0;
+  if (!PRIME && lead && J.first) *J.where = 0;        // (a batch starts with r in its own buffer)
+  if (stop != 0.0) return;
+  if (folds) {                                        // (wave-uniform: tid < 64)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) xq[q] = ipx_wave_sum(xq[q]);
+    const bool mine = xtag == (double)J.it;
+    if (tid == 0) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        J.xs_comp[q * IPX_XS_STRIDE + wg] = mine ? xq[q] : __builtin_nan("");
+    }
+  }
+  // ... and their sum as ipx_fold_regs<1, FU>::finish forms it: lane sums, wave sums, the four
+  // waves' values left to right
+  double alpha = 0.0;
+  if constexpr (!PRIME) {
+    double ptHp;
+    double v = 0.0;
+    if (tid < FW) {
+#pragma unroll
+      for (int u = 0; u < FU; ++u) v += ft[u];
+      for (int i = tid + FU * FW; i < J.np1; i += FW) v += J.p1[i];
+    }
+    v = ipx_wave_sum(v);
+    if (tid < FW && (tid & (IPX_WAVE - 1)) == 0) fold_lds[tid / IPX_WAVE] = v;
+    ipx_lds_barrier();
+    const double t0 = fold_lds[0], t1 = fold_lds[1], t2 = fold_lds[2], t3 = fold_lds[3];
+    ptHp = ((t0 + t1) + t2) + t3;
+    if (rtg < tol) {                                  // qp_subproblem.py:551
+      if (lead) J.st[ST_STOP] = 4.0;
+      return;
+    }
+    if (ptHp <= 0.0) {                                // :558
+      if (lead) { J.st[ST_NITER] += 1.0; J.st[ST_PTHP] = ptHp; J.st[ST_STOP] = 3.0; }
+      return;
+    }
+    alpha = rtg / ptHp;                               // :579
+    if (lead) {
+      J.st[ST_NITER] += 1.0; J.st[ST_PTHP] = ptHp; J.st[ST_ALPHA] = alpha;
+      *J.where = J.dest;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < QSP; ++k) {
+    const int j = tid + k * TB;
+    if (j < nspan) span[j] = PRIME ? sr[k] : sr[k] + alpha * sh[k];   // :622
+  }
+  // A' on the own variables (and x, p for the radius test), requested now: they arrive while the
+  // row sums and the reduction run.  Pairs of variables as in k_solve_pcr.
+  const int64_t vb = av0 & ~1;
+  unsigned ac[QP];
+  v2d aw0[QP], aw1[QP], ax[XN == 0 ? QP : 1], ap[XN == 0 ? QP : 1];
+  {
+    const int64_t last = max((int64_t)av0 + avn - 1, vb) & ~(int64_t)1;
+#pragma unroll
+    for (int k = 0; k < QP; ++k) {
+      const int64_t j = min(vb + 2 * (int64_t)(tid + k * TB), last);
+      ac[k] = *reinterpret_cast<const unsigned *>(J.ell_row + j);
+      aw0[k] = *reinterpret_cast<const v2d *>(J.ell_val + j);
+      aw1[k] = *reinterpret_cast<const v2d *>(J.ell_val + J.n + j);
+      if constexpr (XN == 0) {
+        ax[k] = *reinterpret_cast<const v2d *>(J.x + j);
+        ap[k] = *reinterpret_cast<const v2d *>(J.p + j);
+      }
+    }
+  }
+  ipx_lds_barrier();
+  // w on the window's rows: row sums left to right, every product rounded before it is added
+  {
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < RLA; ++k) {
+      if (k < J.rl) {
+        const int c = row_in ? min(max(first + ao[k], 0), nspan - 1) : 0;
+        sum += av[k] * span[c];
+      }
+    }
+    d[0] = row_in ? 1.0 * sum : 0.0;
+  }
+  const double a0 = a[0], b0 = b[0], w0 = d[0];        // level-0 row kept for the residual
+  for (int i = tid; i < 2 * PAD; i += TB) {
+    const int r = i < PAD ? i : R + i;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) { pa[u][r] = 0.0; pr[u][r] = 1.0; pd[u][r] = 0.0; }
+  }
+  pcr_levels<1, TB>(L, R, tid, a, b, d, pa, pr, pd);
+  if (tid < R) {
+    const double xv = d[0] / b[0];
+    sx[tid] = xv;
+    if (tid >= H && tid < H + rows_wg && grow < m) J.v[grow] = xv;
+  }
+  ipx_lds_barrier();
+  // ---- g = r_next - A'v on this workgroup's variables (k_solve_pcr's tail, r_next out of LDS)
+  double gacc = 0.0, xacc = 0.0;
+#pragma unroll
+  for (int k = 0; k < QP; ++k) {
+    const int64_t j = vb + 2 * (int64_t)(tid + k * TB);
+    const int c0 = H + (int)(ac[k] & 0xffffu), c1 = H + (int)(ac[k] >> 16);
+    const int s0 = (int)min(max(j - c_lo, (int64_t)0), (int64_t)nspan - 1);
+    const int s1 = (int)min(max(j + 1 - c_lo, (int64_t)0), (int64_t)nspan - 1);
+    const double sg = PRIME ? J.sign : 1.0;
+    double y0 = -sg * (aw0[k].x * sx[c0] + aw1[k].x * sx[c0 + 1]);
+    y0 += sg * span[s0];
+    double y1 = -sg * (aw0[k].y * sx[c1] + aw1[k].y * sx[c1 + 1]);
+    y1 += sg * span[s1];
+    const bool in0 = j >= av0 && j < (int64_t)av0 + avn;
+    const bool in1 = j + 1 >= av0 && j + 1 < (int64_t)av0 + avn;
+    if (in0 && in1) {
+      *reinterpret_cast<v2d *>(J.g_out + j) = (v2d){y0, y1};
+      gacc += y0 * y0;
+      gacc += y1 * y1;
+    } else if (in0) {
+      J.g_out[j] = y0;
+      gacc += y0 * y0;
+    } else if (in1) {
+      J.g_out[j + 1] = y1;
+      gacc += y1 * y1;
+    }
+    if constexpr (XN == 0) {
+      const double xn0 = ax[k].x + alpha * ap[k].x;   // :580 (not stored)
+      const double xn1 = ax[k].y + alpha * ap[k].y;
+      if (in0) xacc += xn0 * xn0;
+      if (in1) xacc += xn1 * xn1;
+    }
+  }
+  const double gtot = ipx_block_reduce<IPX_SUM>(gacc, red_lds);
+  if (tid == 0) {
+    J.part3[wg] = gtot;
+    J.part3[gridDim.x + wg] = 0.0;
+  }
+  if constexpr (XN == 0) {
+    const double xtot = ipx_block_reduce<IPX_SUM>(xacc, red_lds);
+    if (tid == 0) {
+      J.part2[wg] = xtot;
+      J.part2[gridDim.x + wg] = 0.0;
+    }
+  }
+  // ---- residual of the own rows (k_solve_pcr's)
+  if (tid < R) pa[0][PAD + tid] = a0;
+  ipx_lds_barrier();
+  double acc = 0.0;
+  if (tid >= H && tid < H + rows_wg && grow < m) {
+    double sum = b0 * sx[tid];
+    sum += a0 * sx[tid - 1];
+    sum += pa[0][PAD + tid + 1] * sx[tid + 1];
+    const double res = w0 - sum;
+    acc += res * res;
+  }
+  const double tot = ipx_block_reduce<IPX_SUM>(acc, red_lds);
+  if (tid == 0) J.part4[wg] = tot;
+}
+
+template <int QV>
+int launch_step1_solve_tail_q(const LevDev &lv, int L, const ipx_fused_proj_job &J, int grid,
+                              hipStream_t st) {
+  const int rows_wg = DEC_CHUNKS * lv.q;
+  if (J.prime) {
+    hipLaunchKernelGGL((k_step1_solve_tail<QV, 1, true>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
+                       rows_wg, L, lv.band, J);
+    IPX_CHECK_LAUNCH();
+    return IPX_OK;
+  }
+  switch (J.xn) {
+    case 0:
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 0>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
+                         rows_wg, L, lv.band, J);
+      break;
+    case 1:
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 1>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
+                         rows_wg, L, lv.band, J);
+      break;
+    default:
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 2>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
+                         rows_wg, L, lv.band, J);
+      break;
+  }
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+// variables per lane of the tail at PCR_TB lanes (launch_solve_pcr's count)
+int pcr_tail_per_lane(int qv) { return (qv * (DOWN_T - IPX_WAVE) + 1 + PCR_TB - 1) / PCR_TB; }
 
 
 template <int K>
@@ -2807,6 +3102,44 @@ int ipx_banded_solve_resid_atv_launch(void *handle, const double *w, double *x, 
     case 4: return launch_solve_decoupled<4>(lv, w, x, h->rinv, partial, npartial, guard, st, &job, qv);
   }
   return IPX_EINVAL;
+}
+
+// The projection half of a CG iteration in one launch (k_step1_solve_tail): only on the cyclic-
+// reduction path of a tridiagonal A A', a window of at most PCR_TB rows, rows of A and spans
+// within the kernel's registers / LDS, a tail of at most 6 variables per lane.
+int ipx_banded_fused_proj_ok(void *handle, int rl, int64_t nspan, int qv) {
+  int32_t geo[2];
+  if (!handle || !ipx_banded_decoupled_geometry(handle, geo)) return IPX_EUNSUPPORTED;
+  Banded *h = (Banded *)handle;
+  if (h->pcr_L <= 0 || h->lev[0].k != 1 || geo[0] + 2 * (1 << h->pcr_L) > PCR_TB)
+    return IPX_EUNSUPPORTED;
+  if (rl < 1 || rl > IPX_FP_ROW || nspan < 1 || nspan > IPX_FP_SPAN || qv < 1 ||
+      pcr_tail_per_lane(qv) > 6)
+    return IPX_EUNSUPPORTED;
+  return IPX_OK;
+}
+
+int ipx_banded_fused_proj_launch(void *handle, const ipx_fused_proj_job &job, int *npartial,
+                                 hipStream_t st) {
+  if (job.prime ? (job.xn != 1 || (job.sign != 1.0 && job.sign != -1.0))
+                : (!job.st || !job.p1 || !job.Hp || !job.where))
+    return IPX_EINVAL;
+  if (!job.r_in || !job.g_out || job.g_out == job.r_in ||
+      !job.A_ell_val || !job.A_ell_off16 || !job.A_rowfirst || !job.win || !job.vown ||
+      !job.ell_row || !job.ell_val || !job.v || !job.part3 || !job.part4 ||
+      (job.n & 1) || (job.xn == 0 && (!job.x || !job.p || !job.part2)) ||
+      (job.xn == 2 && (!job.xs_raw || !job.xs_comp || job.nraw < 1)) || job.xn < 0 || job.xn > 2)
+    return IPX_EINVAL;
+  if (ipx_banded_fused_proj_ok(handle, job.rl, 1, job.qv) != IPX_OK) return IPX_EUNSUPPORTED;
+  Banded *h = (Banded *)handle;
+  const LevDev lv = to_dev(h->lev[0], nullptr);
+  const int grid = (lv.P + DEC_CHUNKS - 1) / DEC_CHUNKS;
+  if (job.xn == 2 && job.ncomp > grid) return IPX_EINVAL;
+  if (npartial) *npartial = grid;
+  const int per = pcr_tail_per_lane(job.qv);
+  if (per <= 2) return launch_step1_solve_tail_q<2>(lv, h->pcr_L, job, grid, st);
+  if (per <= 4) return launch_step1_solve_tail_q<4>(lv, h->pcr_L, job, grid, st);
+  return launch_step1_solve_tail_q<6>(lv, h->pcr_L, job, grid, st);
 }
 
 // The cyclic-reduction form of the single-launch solve as the resident CG kernel

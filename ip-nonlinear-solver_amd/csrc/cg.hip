@@ -32,6 +32,11 @@
 // each falling back to the separate launches when its structural condition fails
 // (checked symbolically by ipsolver/cg_fused.py).
 //
+// ... and, beyond the resident kernel's size, into TWO: the first two as k_step1_solve_tail
+// (banded.hip; rows of A of one length <= 16, the cyclic-reduction solve).  g then lands in the
+// buffer r was not read from: inside a batch r and r_next swap roles by iteration, and
+// cg_iterate ends with one guarded copy (k_cg_settle_r) that leaves the current r in a->r.
+//
 // Because x is only advanced in step2, every early exit leaves (x, p, alpha)
 // exactly as the reference's exit paths (:565-576, :585-596) need them.
 //
@@ -464,8 +469,8 @@ struct ipx_xsums_job {
   const double *in;
   int it, write;
 };
-constexpr int XS_SLICE = 64;     // raw partials per folded sum (one wave of k_cg_step1_ar)
-constexpr int XS_STRIDE = IPX_BLOCK;   // distance of the three arrays of folded sums
+constexpr int XS_SLICE = IPX_XS_SLICE;     // raw partials per folded sum (one wave of k_cg_step1_ar)
+constexpr int XS_STRIDE = IPX_XS_STRIDE;   // distance of the three arrays of folded sums
 constexpr double XS_BAND = 1e-9; // the carried form decides :583 only outside this relative band
 
 // C16: the column indices come as 16-bit offsets into the tile's span (col - c_lo, built once
@@ -1055,6 +1060,17 @@ k_cg_save_pb(const double *__restrict__ p, const int32_t *__restrict__ tiles, in
   pb[(int64_t)ntiles * 2 * hmax + idx] = v;
 }
 
+// PJ_STEP1_SOLVE_TAIL: r <- r_next when the batch's last projection left the current r there
+// (*where != 0; every workgroup reads the word, nobody writes it: the next batch's first launch
+// clears it).
+__global__ void __launch_bounds__(VB)
+k_cg_settle_r(int64_t n, const int32_t *__restrict__ where, const double *__restrict__ src,
+              double *__restrict__ dst) {
+  if (*where == 0) return;
+  for (int64_t i = (int64_t)blockIdx.x * VB + threadIdx.x; i < n; i += (int64_t)gridDim.x * VB)
+    dst[i] = src[i];
+}
+
 // Voids the tag of the carried sums (ipx_cg_args.xsums) on the stream.
 __global__ void k_xsums_void(double *xs_tag) { *xs_tag = 0.0; }
 
@@ -1185,8 +1201,10 @@ k_cg_pack_comm(RangeJob job, double *__restrict__ out, ipx_peer_view pv, uint32_
 enum Step1Form { S1_VECTOR, S1_BOX, S1_FUSED_AR };
 // projection: m = 0, g = r | box-Schur, the box rows never multiplied as matrix rows | banded
 // solve with g = r - A'v as its tail (one launch) | banded or box-Schur solve, then the A' SpMV |
-// dense matvecs w = A r, v = G^-1 w, g = r - A'v, t = A g
-enum ProjForm { PJ_NONE, PJ_BOX, PJ_SOLVE_TAIL, PJ_SOLVE_SPMV, PJ_DENSE };
+// dense matvecs w = A r, v = G^-1 w, g = r - A'v, t = A g | step1, w = A r_next, the banded
+// solve and its tail as one launch on the solve's windows (csrc/banded.hip k_step1_solve_tail:
+// step1 stays S1_FUSED_AR, whose radius modes it takes over, but launches nothing of its own)
+enum ProjForm { PJ_NONE, PJ_BOX, PJ_SOLVE_TAIL, PJ_SOLVE_SPMV, PJ_DENSE, PJ_STEP1_SOLVE_TAIL };
 // step2: k_cg_step2, then H.p | k_cg_step2_hp, step2 inside the H.p SpMV (banded H)
 enum Step2Form { S2_VECTOR, S2_FUSED_HP };
 // H.p: the caller's, between the iterations | a low-rank term (+ diagonal) alone | row-major
@@ -1251,17 +1269,24 @@ LoopPlan plan_of(const ipx_cg_args *a) {
   P.proj = a->m <= 0 ? PJ_NONE : box ? PJ_BOX : tail ? PJ_SOLVE_TAIL : PJ_SOLVE_SPMV;
   P.step2 = P.fused_hp ? S2_FUSED_HP : S2_VECTOR;
   P.no_xn2 = fused_ar && a->no_radius != 0;
-  P.xsums = a->xsums != nullptr && fused_ar && P.fused_hp && a->no_radius == 0 &&
-            P.xs_ncomp <= (int)a->A_ntiles && P.xs_ncomp <= XS_STRIDE;
   P.np4 = a->m > 0 ? ipx_banded_resid_count(a->solver_kind == 1 ? (b ? b->inner : nullptr)
                                                                 : a->banded) : 1;
+  // the projection half as one launch: asked for, every table bound, and no resident launch
+  if (a->fused_proj != 0 && fused_ar && P.proj == PJ_SOLVE_TAIL && a->At_ell_row &&
+      a->At_ell_val && a->A_ell_val && a->A_ell_off16 && a->A_rowfirst && a->P_win &&
+      a->r_where && a->n % 2 == 0 && !ipx_cg_resident_ok(a) &&
+      ipx_banded_fused_proj_ok(a->banded, (int)a->A_rl, a->P_nspan, (int)a->At_qv) == IPX_OK)
+    P.proj = PJ_STEP1_SOLVE_TAIL;
+  const int xs_wgs = P.proj == PJ_STEP1_SOLVE_TAIL ? P.np4 : (int)a->A_ntiles;   // who folds them
+  P.xsums = a->xsums != nullptr && fused_ar && P.fused_hp && a->no_radius == 0 &&
+            P.xs_ncomp <= xs_wgs && P.xs_ncomp <= XS_STRIDE;
   if (box) {
     const int64_t per = (int64_t)IPX_BLOCK * step1_box_rounds(b);
     P.np2 = (int)((b->ng + b->ngen + per - 1) / per);
     P.np3 = ipx_boxschur_project_count(b);
   } else {
-    P.np2 = fused_ar ? (int)a->A_ntiles : (int)a->vec_grid;
-    P.np3 = P.proj == PJ_SOLVE_TAIL ? P.np4 : (int)a->At_ntiles;
+    P.np2 = P.proj == PJ_STEP1_SOLVE_TAIL ? P.np4 : fused_ar ? (int)a->A_ntiles : (int)a->vec_grid;
+    P.np3 = P.proj == PJ_SOLVE_TAIL || P.proj == PJ_STEP1_SOLVE_TAIL ? P.np4 : (int)a->At_ntiles;
   }
   return P;
 }
@@ -1387,7 +1412,8 @@ int launch_step1_ar(const ipx_cg_args *a, const LoopPlan &P, int it, const doubl
 template <bool PEER>
 int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double *p2, int np2,
                     const double *p3, int np3, const double *p4, int np4,
-                    typename peer_arg<PEER>::type pj, const ipx_xsums_job &xs, hipStream_t st) {
+                    typename peer_arg<PEER>::type pj, const ipx_xsums_job &xs, hipStream_t st,
+                    const double *g = nullptr) {
   const bool xsum = xs.raw != nullptr && (xs.write != 0 || (mode & 4) != 0);
   if ((mode & 4) && (!xsum || !xs.in || PEER || a->lb)) return IPX_EINVAL;
   // H_tile_rows: the longest tile's row count (set by the host binding)
@@ -1401,7 +1427,7 @@ int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double *p2, in
   double *g_halo = PEER ? a->r : nullptr;
   hipLaunchKernelGGL(k, dim3(ipx_xcd_grid((int)a->H_ntiles)), dim3(IPX_BLOCK), 0, st, (int)a->n,
                      a->state, it & 1, mode, p2, np2, p3, np3, p4, np4, a->x, a->p,
-                     (const double *)a->r, a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles,
+                     g ? g : (const double *)a->r, a->H_rowptr, a->H_colidx, a->H_val, a->H_tiles,
                      (int)a->H_ntiles, a->H_diag, a->Hp, a->part1, (int)a->H_hmax, pb_in, pb_out,
                      (const uint16_t *)a->H_col16, a->H_rowlen, pj, g_halo, xs);
   IPX_CHECK_LAUNCH();
@@ -1505,6 +1531,10 @@ struct HalfArgs {
   // the carried sums the fused step2 + H.p writes and reads (the batch loop's alone)
   ipx_xsums_job xs{nullptr, nullptr, it, 0};
   hipEvent_t *ev = nullptr;             // ipx_cg_iterate_timed's events of this iteration
+  // PJ_STEP1_SOLVE_TAIL: the roles of r and r_next alternate inside a batch -- flip = the
+  // current r lives in r_next (and g goes to r); first = the batch's first iteration
+  bool flip = false, first = true;
+  const double *g = nullptr;            // where this iteration's g is (NULL: a->r)
 };
 #define MARK(i) do { if (h.ev) (void)hipEventRecord(h.ev[i], st); } while (0)
 
@@ -1520,6 +1550,32 @@ int launch_projection_half(const ipx_cg_args *a, const LoopPlan &P, const HalfAr
     h.cmp->add(p1, np1, 2, 2048);      // beyond what a consumer folds in one or two rounds
     rc = h.cmp->launch(st);
     if (rc) return rc;
+  }
+  if (P.proj == PJ_STEP1_SOLVE_TAIL) {
+    if (h.peer || h.own) return IPX_EINVAL;
+    const bool carried = (h.mode & 4) != 0;
+    if (carried && ((h.mode & 1) || !a->xsums)) return IPX_EINVAL;
+    const int nraw = carried ? (int)a->H_ntiles : 0;
+    ipx_fused_proj_job J{};
+    J.st = a->state; J.parity = h.it & 1; J.p1 = p1 + np1; J.np1 = np1;
+    J.r_in = h.flip ? a->r_next : a->r; J.Hp = a->Hp; J.g_out = h.flip ? a->r : a->r_next;
+    J.xn = carried ? 2 : (h.mode & 1) ? 1 : 0;
+    J.x = a->x; J.p = a->p; J.part2 = a->part2;
+    J.xs_raw = carried ? a->xsums : nullptr; J.nraw = nraw;
+    J.xs_comp = carried ? a->xsums + 3 * nraw + 1 : nullptr;
+    J.ncomp = carried ? P.xs_ncomp : 0; J.it = h.it;
+    J.A_ell_val = a->A_ell_val; J.A_ell_off16 = (const uint16_t *)a->A_ell_off16;
+    J.A_rowfirst = a->A_rowfirst; J.rl = (int)a->A_rl; J.win = a->P_win; J.n = a->n;
+    J.vown = a->At_vown; J.qv = (int)a->At_qv; J.ell_row = a->At_ell_row; J.ell_val = a->At_ell_val;
+    J.v = a->v; J.part3 = a->part3; J.part4 = a->part4;
+    J.where = a->r_where; J.first = h.first ? 1 : 0; J.dest = h.flip ? 0 : 1;
+    MARK(1); MARK(2);
+    int np = 0;
+    rc = ipx_banded_fused_proj_launch(a->banded, J, &np, st);
+    if (rc) return rc;
+    *np2 = *np3 = *np4 = np;
+    MARK(3); MARK(4); MARK(5);
+    return IPX_OK;
   }
   const bool fuse1 = P.step1 == S1_FUSED_AR;
   const OwnRanges own = h.own ? *h.own : own_all(a->n);
@@ -1607,6 +1663,8 @@ int launch_projection_half(const ipx_cg_args *a, const LoopPlan &P, const HalfAr
       MARK(5);
       break;
     }
+    case PJ_STEP1_SOLVE_TAIL:
+      return IPX_EINVAL;                             // (launched above)
     case PJ_DENSE: {
       // Dense Jacobian (BASELINE config 2): A (m x n) and A' (n x m) row major in A_val /
       // At_val, `banded` = G^-1 (M x M, M = m rounded up to 32; w and v are M long with a zero
@@ -1648,17 +1706,19 @@ int launch_update_half(const ipx_cg_args *a, const LoopPlan &P, const HalfArgs &
     rc = h.cmp->launch(st);
     if (rc) return rc;
   }
+  // g: a->r, or under PJ_STEP1_SOLVE_TAIL whichever of r / r_next this iteration's launch wrote
+  const double *g = h.g ? h.g : a->r;
   if (P.step2 == S2_FUSED_HP) {
     MARK(6);
     rc = h.peer ? launch_step2_hp<true>(a, h.it, h.mode, p2, np2, p3, np3, p4, np4, *h.peer, h.xs,
                                         st)
                 : launch_step2_hp<false>(a, h.it, h.mode, p2, np2, p3, np3, p4, np4,
-                                         ipx_no_peer{}, h.xs, st);
+                                         ipx_no_peer{}, h.xs, st, g);
     if (!rc && P.lowrank_tail) rc = launch_lowrank(a, true, h.guard, st);
   } else {
     if (h.peer) return IPX_EINVAL;                   // (no PEER form: see peer_fusable)
     hipLaunchKernelGGL(k_cg_step2, dim3(ipx_xcd_grid((int)a->vec_grid)), dim3(VB), 0, st, a->n,
-                       a->state, h.it & 1, h.mode, p2, np2, p3, np3, p4, np4, a->x, a->p, a->r,
+                       a->state, h.it & 1, h.mode, p2, np2, p3, np3, p4, np4, a->x, a->p, g,
                        (int)a->vec_grid);
     IPX_CHECK_LAUNCH();
     MARK(6);
@@ -1706,11 +1766,21 @@ int cg_iterate(const ipx_cg_args *a, const LoopPlan &P, int32_t it_begin, int32_
     h.xs = ipx_xsums_job{a->xsums, carried ? a->xsums + 3 * a->H_ntiles + 1 : nullptr, it,
                          P.xsums ? 1 : 0};
     h.ev = ev;
+    h.first = it == it_begin;
+    h.flip = P.proj == PJ_STEP1_SOLVE_TAIL && ((it - it_begin) & 1) != 0;
+    if (P.proj == PJ_STEP1_SOLVE_TAIL) h.g = h.flip ? a->r : a->r_next;
     int np2 = 0, np3 = 0, np4 = 0;
     int rc = launch_projection_half(a, P, h, a->part1, P.np1, &np2, &np3, &np4, st);
     if (rc) return rc;
     rc = launch_update_half(a, P, h, a->part2, np2, a->part3, np3, a->part4, np4, st);
     if (rc) return rc;
+  }
+  if (P.proj == PJ_STEP1_SOLVE_TAIL && it_end > it_begin) {
+    // the current r back into a->r where the batch left it in r_next (an odd number of
+    // projections ran: the word says so, whatever stopped the batch and where)
+    hipLaunchKernelGGL(k_cg_settle_r, dim3(ipx_grid_for(a->n, VB * 4, 1024)), dim3(VB), 0, st, a->n,
+                       a->r_where, (const double *)a->r_next, a->r);
+    IPX_CHECK_LAUNCH();
   }
   return IPX_OK;
 }
@@ -2250,9 +2320,20 @@ static int prime_project(const ipx_cg_args *a, const ipx_csr_view &A, const ipx_
 // of ||z||^2 (pz) and of ||w - (A A') v||^2 = ||A z||^2 (pt: the orthogonality measure the
 // loop's iterations use, projections.py:52 without a second product by A) -- two launches
 // instead of four.  guard: *guard != 0 skips both (a correction step that is not due).
-static int prime_project_tail(const ipx_cg_args *a, const ipx_csr_view &A, const double *x,
-                              double *z, double *pz, double *pt, int *np, double sign,
-                              const double *guard, hipStream_t st) {
+// Under PJ_STEP1_SOLVE_TAIL both are ONE launch, the loop's fused projection without its step
+// (k_step1_solve_tail<.., PRIME>) -- where z is not x: a workgroup reads x on its whole window.
+static int prime_project_tail(const ipx_cg_args *a, const LoopPlan &P, const ipx_csr_view &A,
+                              const double *x, double *z, double *pz, double *pt, int *np,
+                              double sign, const double *guard, hipStream_t st) {
+  if (P.proj == PJ_STEP1_SOLVE_TAIL && x != z) {
+    ipx_fused_proj_job J{};
+    J.r_in = x; J.g_out = z; J.xn = 1; J.prime = 1; J.sign = sign; J.guard = guard;
+    J.A_ell_val = a->A_ell_val; J.A_ell_off16 = (const uint16_t *)a->A_ell_off16;
+    J.A_rowfirst = a->A_rowfirst; J.rl = (int)a->A_rl; J.win = a->P_win; J.n = a->n;
+    J.vown = a->At_vown; J.qv = (int)a->At_qv; J.ell_row = a->At_ell_row; J.ell_val = a->At_ell_val;
+    J.v = a->v; J.part3 = pz; J.part4 = pt;
+    return ipx_banded_fused_proj_launch(a->banded, J, np, st);
+  }
   int rc = ipx_spmv_launch(A, x, 1.0, nullptr, 0.0, nullptr, a->w, nullptr, guard, st);
   if (rc) return rc;
   return ipx_banded_solve_resid_atv_launch(a->banded, a->w, a->v, pt, np, a->At_rowptr,
@@ -2265,14 +2346,16 @@ static int prime_project_tail(const ipx_cg_args *a, const ipx_csr_view &A, const
 static int prime_project_any(const ipx_cg_args *a, const LoopPlan &P, const ipx_csr_view &A,
                              const ipx_csr_view &At, const double *x, double *z, PrimeRed &R,
                              int base, bool have_xnorm, double sign, hipStream_t st) {
-  if (P.proj != PJ_SOLVE_TAIL) return prime_project(a, A, At, x, z, R, base, have_xnorm, sign, st);
+  // (PJ_STEP1_SOLVE_TAIL: the priming's projections are the solve-with-tail pair all the same)
+  if (P.proj != PJ_SOLVE_TAIL && P.proj != PJ_STEP1_SOLVE_TAIL)
+    return prime_project(a, A, At, x, z, R, base, have_xnorm, sign, st);
   int rc = have_xnorm ? IPX_OK : ipx_norms(a->n, x, R.red + base + 4, R.ws + R.off, st);
   if (rc) return rc;
   const int cap = (int)((a->m + 255) / 256) + 8;
   double *pz = R.ws + R.off, *pt = pz + 2 * cap;
   R.off += 3 * (int64_t)cap;
   int np = 0;
-  rc = prime_project_tail(a, A, x, z, pz, pt, &np, sign, nullptr, st);
+  rc = prime_project_tail(a, P, A, x, z, pz, pt, &np, sign, nullptr, st);
   if (rc) return rc;
   R.single(pz, np, base);
   R.single(pt, np, base + 2);
@@ -2294,7 +2377,7 @@ static int prime_project_stepped(const ipx_cg_args *a, const LoopPlan &P,
   const int n0 = R.f.n;
   int rc;
   const double *skip = R.red + PR_SKIP + pj;
-  if (P.proj == PJ_SOLVE_TAIL) {
+  if (P.proj == PJ_SOLVE_TAIL || P.proj == PJ_STEP1_SOLVE_TAIL) {
     if (!have_xnorm) {
       rc = ipx_norms(a->n, x, R.red + base + 4, R.ws + R.off, st);
       if (rc) return rc;
@@ -2303,7 +2386,7 @@ static int prime_project_stepped(const ipx_cg_args *a, const LoopPlan &P,
     double *pz = R.ws + R.off, *pt = pz + 2 * cap, *cz = pt + cap, *ct = cz + 2 * cap;
     R.off += 6 * (int64_t)cap;
     int np = 0, npc = 0;
-    rc = prime_project_tail(a, A, x, z, pz, pt, &np, sign, nullptr, st);
+    rc = prime_project_tail(a, P, A, x, z, pz, pt, &np, sign, nullptr, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_prime_decide, dim3(1), dim3(IPX_BLOCK), 0, st, R.red, pz, np, pt, np, 0,
                        base, xslot, pj, orth_tol, norm_A, canc2, norm_A2_dev,
@@ -2311,7 +2394,7 @@ static int prime_project_stepped(const ipx_cg_args *a, const LoopPlan &P,
     IPX_CHECK_LAUNCH();
     // the step: z <- z - A'(A A')^-1 (A z), the same two launches on z itself (in place: the
     // tail reads and writes one variable per lane), guarded
-    rc = prime_project_tail(a, A, z, z, cz, ct, &npc, 1.0, skip, st);
+    rc = prime_project_tail(a, P, A, z, z, cz, ct, &npc, 1.0, skip, st);
     if (rc) return rc;
     *step = PrimeStep{cz, ct, npc, npc, base, pj, 0};
     return IPX_OK;
@@ -2481,6 +2564,12 @@ int ipx_cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, void 
 // step1, spmv A r, banded solve, spmv r-A'v, spmv A g, step2, spmv H p.
 // Slower than ipx_cg_iterate (event records between kernels) -- use it for
 // per-kernel attribution, not for the throughput number.
+// Under the fused projection (PJ_STEP1_SOLVE_TAIL) the one launch of the projection half is
+// booked under "banded solve" (the classes before and behind it read 0).  The iterations are
+// enqueued one cg_iterate call each, so every one of them ends with the guarded copy
+// k_cg_settle_r moving r_next back into r (8 n bytes each way) -- behind the iteration's last
+// event and before the next one's first: in no class, but in the wall clock of this entry;
+// the batch loop launches it once per call and copies only after an odd count.
 #define IPX_CG_NCLASS 7
 int ipx_cg_iterate_timed(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, float *ms_out,
                          void *stream) {

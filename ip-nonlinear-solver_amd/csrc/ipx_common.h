@@ -694,6 +694,42 @@ int ipx_banded_solve_resid_atv_launch(void *handle, const double *w, double *x, 
                                       double sign = 1.0);
 int ipx_banded_solve_resid_launch(void *handle, const double *w, double *x, double *partial,
                                   int *npartial, const double *guard, hipStream_t st);
+// The projection half of a CG iteration as ONE launch on the cyclic-reduction solve's windows
+// (csrc/banded.hip k_step1_solve_tail): step1's scalars, r_next = r + alpha Hp on the window's
+// column span (LDS), w = A r_next on the window's rows (registers), the solve, g = r_next - A'v
+// on the workgroup's own variables.  What the kernel reads beside the factorization:
+constexpr int IPX_XS_SLICE = 64;            // raw partials per folded carried sum (one wave)
+constexpr int IPX_XS_STRIDE = IPX_BLOCK;    // distance of the three arrays of folded sums
+constexpr int IPX_FP_SPAN = 4096;           // span columns per workgroup (LDS)
+constexpr int IPX_FP_ROW = 16;              // entries per row of A (registers)
+struct ipx_fused_proj_job {
+  double *st;                     // the loop's state block
+  int parity;                     // it & 1
+  const double *p1; int np1;      // the p'Hp partials (the half that holds them) and their count
+  const double *r_in, *Hp;        // r, H p: read over the whole span
+  double *g_out;                  // g on the own variables: NOT r_in (neighbours still read it)
+  int xn;                         // 0: ||x + alpha p||^2 partials from x and p (part2, one per
+  const double *x, *p;            //    workgroup, second half zero); 1: not formed; 2: the first
+  double *part2;                  //    xs_ncomp workgroups fold their slice of the carried sums
+  const double *xs_raw; int nraw; double *xs_comp; int ncomp; int it;
+  // A in ELL-transposed form (entry k of row i at [k * m + i]; the column as rowfirst[i] + off16)
+  const double *A_ell_val; const uint16_t *A_ell_off16; const int32_t *A_rowfirst; int rl;
+  const int32_t *win;             // per workgroup: first / one past the last column of its span
+  int64_t n;
+  const int32_t *vown; int qv;    // A' (ELL(2)) on the own variables: see AtvJob
+  const uint16_t *ell_row; const double *ell_val;
+  double *v, *part3, *part4;
+  // where the current r lives (0: the loop's r, 1: its r_next): the first launch of a batch
+  // clears the word, every launch that stores g writes `dest`
+  int32_t *where; int first, dest;
+  // prime != 0: the projection alone (the priming): st, p1, Hp, where unused; xn = 1;
+  // g = sign (r_in - A'v); *guard != 0 (or NULL: never) skips the launch
+  int prime; double sign; const double *guard;
+};
+// IPX_EUNSUPPORTED when the factorization, the window or the tables do not fit the kernel
+int ipx_banded_fused_proj_ok(void *handle, int rl, int64_t nspan, int qv);
+int ipx_banded_fused_proj_launch(void *handle, const ipx_fused_proj_job &job, int *npartial,
+                                 hipStream_t st);
 // partial[0..*npartial) <- per-workgroup sums of ||w - (A A') v||^2 (<= 256 of them)
 int ipx_banded_residual_launch(void *handle, const double *w, const double *v, double *partial,
                                int *npartial, const double *guard, hipStream_t st);

@@ -255,8 +255,12 @@ def load():
 #                      device chains (csrc/sqp.hip)
 #   no-lowrank-loop    a quasi-Newton Hessian term applied by the host between the CG loop's
 #                      iterations (the operator form) instead of inside its launches
+#   no-fused-projection  problems beyond the resident kernel's size: step1 + A.r, the solve with
+#                      its tail and step2 + H.p as three launches per iteration instead of the
+#                      projection half as one (csrc/banded.hip k_step1_solve_tail)
 DEBUG_FORMS = ("no-fuse", "no-resident", "no-compact-groups", "no-affine-groups", "keep-xn2",
-               "read-xn2", "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop")
+               "read-xn2", "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop",
+               "no-fused-projection")
 
 
 def debug_form(name):

@@ -47,7 +47,9 @@ class CgArgs(ctypes.Structure):
         ("P_navn", _I64), ("H_operator", _I64),
         ("resident", _I64), ("R_ll", _P), ("R_hw", _I64), ("R_seq", _P),
         ("LR_W", _P), ("LR_state", _P), ("LR_part", _P), ("LR_mem", _I64), ("LR_rows", _I64),
-        ("xsums", _P), ("xsums_carry", ctypes.c_int32))]
+        ("xsums", _P),
+        ("fused_proj", _I64), ("A_ell_val", _P), ("A_ell_off16", _P), ("r_where", _P),
+        ("xsums_carry", ctypes.c_int32))]
 
 
 # Counters over the life of the process (diagnostics: how often the device loop
@@ -328,6 +330,7 @@ def ell_rows(At, row_rel):
 
 
 _RES_LIMITS = None
+FUSED_MIN_BATCH = 16    # iterations from which a batch pays for the ELL-transposed copy of A
 
 
 def resident_limits():
@@ -396,6 +399,39 @@ def fuse_project(pattern, vown_h, rows_wg, nwg, H):
                            torch.from_numpy(win).to(dev), nspan, avn, hw, inner)
     pattern._ipx_project = (key, out)
     return out
+
+
+def ell_transposed(A, rl):
+    """A Jacobian whose rows all have ``rl`` entries (``fuse_project``'s check) once more in
+    ELL-transposed form for the fused projection kernel (csrc/banded.hip k_step1_solve_tail: one
+    lane per row, consecutive lanes consecutive rows): ``(off16, val)`` with entry k of row i at
+    ``[k * m + i]`` -- the column as a 16-bit offset from the row's first column, the entries in
+    their CSR order.  The offsets and the gather map are symbolic (cached on the pattern); the
+    values are one gather per new value array, like ``ell_rows``."""
+    done = getattr(A, "_ipx_ellt_done", None)          # same matrix object: same values
+    if done is not None and done[0] == rl:
+        return done[1], done[2]
+    pat = A.pattern
+    cache = getattr(pat, "_ipx_ellt", None)
+    if cache is None or cache[0] != rl:
+        m = pat.shape[0]
+        assert pat.nnz == m * rl
+        rows = pat.indices_h.astype(np.int64).reshape(m, rl)
+        off = rows - rows.min(axis=1)[:, None]
+        assert off.min() >= 0 and off.max() < 65536
+        src = (np.arange(m, dtype=np.int64)[None, :] * rl
+               + np.arange(rl, dtype=np.int64)[:, None]).ravel()
+        assert src.size == 0 or (src.min() >= 0 and src.max() < pat.nnz)
+        dev = ctx().device
+        cache = pat._ipx_ellt = (
+            rl, torch.from_numpy(np.ascontiguousarray(off.T).ravel().astype(np.uint16)
+                                 .view(np.int16)).to(dev),
+            torch.from_numpy(src.astype(np.int32)).to(dev))
+    _, off16, src = cache
+    val = torch.empty(src.numel(), dtype=torch.float64, device=off16.device)
+    _hip.call("ipx_gather", src.numel(), _p(A.val), _p(src), None, None, _p(val), stream_ptr())
+    A._ipx_ellt_done = (rl, off16, val)
+    return off16, val
 
 
 def _solver_kind(solver):
@@ -470,7 +506,9 @@ def _loop_for(H, P, lb, ub):
             L.args.resident = 0
         return L, key
     POOL_STATS["built"] += 1
-    L = _Loop(H, P, lb, ub, resident=False if key in _NO_RESIDENT else None)
+    # (arm=False: the fused projection's tables bound, its copy of A not made -- the call arms
+    # the form where it pays, arm_fused_projection)
+    L = _Loop(H, P, lb, ub, resident=False if key in _NO_RESIDENT else None, arm=False)
     L.enqueued = None            # (the batch ipx_cg_prime enqueued behind the priming, if any)
     return L, key
 
@@ -504,7 +542,11 @@ class _Loop:
                 return False
             if self.pcr_L is not None and \
                     int(lib.ipx_banded_pcr_level(ctypes.c_void_p(P.solver.handle))) != self.pcr_L:
-                return False            # the resident kernel's windows follow 2^L
+                if getattr(self, "proj_tabs", None) is not None:
+                    return False        # the resident kernel's windows follow 2^L
+                # (so do the fused projection's: without the resident tables the object lives
+                # on, on the three launches -- as before that form existed)
+                self.fp_tabs, self.pcr_L = None, None
             a.banded = ctypes.c_void_p(P.solver.handle)
         else:
             a.banded = ctypes.cast(ctypes.pointer(P.solver.c_args()), ctypes.c_void_p)
@@ -518,6 +560,10 @@ class _Loop:
         if a.At_ell_val:
             self.ell_row, self.ell_val = ell_rows(At, self.row_rel)
             a.At_ell_row, a.At_ell_val = _ptr(self.ell_row), _ptr(self.ell_val)
+        # (the ELL-transposed copy of A is NOT refreshed here: a gather of all of A's values per
+        # new Jacobian costs more than the fused projection saves on a short call -- the caller
+        # arms the form where it pays, arm_fused_projection)
+        a.fused_proj = 0
         a.no_radius = 0
         a.xsums_carry = 0
         if self.xsums is not None:
@@ -525,6 +571,29 @@ class _Loop:
         self.x = torch.empty(self.n, dtype=torch.float64, device=self.state.device)
         a.x = _ptr(self.x)
         self.keep = (A, At, Hc, Hd, lb, ub, P, LR)
+        return True
+
+    def arm_fused_projection(self, iterations=None):
+        """Switch the fused projection (ipx_cg_args.fused_proj) on for the launches that follow,
+        where its tables are bound; True when it is on.  The kernel reads A from an
+        ELL-transposed copy, one gather of all of A's values per new value array
+        (``ell_transposed``: 17-34 us at 1.5e6 entries, plus a host call), against ~2.4 us the
+        form saves per iteration: with ``iterations`` given (what the caller is about to
+        enqueue) and the copy not current, it is only made for FUSED_MIN_BATCH iterations or
+        more; without, unconditionally.  Only between entry-point calls that start from a
+        settled state (a call's beginning, a batch that ended with stop code 0): the layout of
+        part2 follows the form."""
+        if getattr(self, "fp_tabs", None) is None:
+            return False
+        a, A = self.args, self.keep[0]
+        done = getattr(A, "_ipx_ellt_done", None)
+        current = done is not None and done[0] == self.fp_tabs[2]
+        if not current and iterations is not None and iterations < FUSED_MIN_BATCH:
+            a.fused_proj = 0
+            return False
+        self.A_ell_off16, self.A_ell_val = ell_transposed(A, self.fp_tabs[2])
+        a.A_ell_off16, a.A_ell_val = _ptr(self.A_ell_off16), _ptr(self.A_ell_val)
+        a.fused_proj = 1
         return True
 
     def _bind_lowrank(self, LR):
@@ -546,10 +615,11 @@ class _Loop:
             count = max(count, _hip.load().ipx_lowrank_grid(lr.mem.n))
         return 2 * max(count, 1)
 
-    def __init__(self, H, P, lb, ub, resident=None):
+    def __init__(self, H, P, lb, ub, resident=None, fused_projection=None, arm=True):
         from .dense import DeviceDense
         self.geometry, self.pcr_L, self.operator = None, None, None
         self.xsums = None
+        self.fp_tabs = None          # window tables of the fused projection, when bound
         if isinstance(P.A, DeviceDense):
             self._init_dense(H, P, lb, ub)
             return
@@ -667,15 +737,37 @@ class _Loop:
                     L_pcr = int(lib.ipx_banded_pcr_level(ctypes.c_void_p(P.solver.handle)))
                     if resident is None and _hip.debug_form("no-resident"):
                         resident = False
-                    if kS == 1 and L_pcr > 0 and lb is None and hmax > 0 and resident is not False \
-                            and int(np.max(np.diff(Hc.pattern.indptr_h))) <= resident_limits()["row_H"]:
-                        pj = fuse_project(A.pattern, self.vown.cpu().numpy().astype(np.int64),
-                                          geo[0], geo[1], 1 << L_pcr)
-                        if pj is not None and hmax <= pj[7]:
+                    want_res = kS == 1 and L_pcr > 0 and lb is None and hmax > 0 \
+                        and resident is not False \
+                        and int(np.max(np.diff(Hc.pattern.indptr_h))) <= resident_limits()["row_H"]
+                    # where the solve has more workgroups than a resident launch can hold: the
+                    # projection half of an iteration as ONE launch on the solve's windows
+                    # (csrc/banded.hip k_step1_solve_tail), two launches per iteration.  Below
+                    # that size the resident kernel is the production form and the three
+                    # launches its fall-back.  fused_projection=True / False forces it either way.
+                    if fused_projection is None:
+                        fused_projection = geo[1] > resident_limits()["max_wg"] \
+                            and not _hip.debug_form("no-fused-projection")
+                    want_fp = bool(fused_projection) and kS == 1 and L_pcr > 0 and lb is None \
+                        and own is not None and n % 2 == 0
+                    pj = fuse_project(A.pattern, self.vown.cpu().numpy().astype(np.int64),
+                                      geo[0], geo[1], 1 << L_pcr) if (want_res or want_fp) else None
+                    res_ok = pj is not None and want_res and hmax <= pj[7]
+                    if pj is not None and (want_fp or res_ok):
+                        # (the window tables serve both forms; proj_tabs says that THIS problem
+                        # qualifies for the resident launch -- the sharded group's agreement reads
+                        # it --, fp_tabs that the fused projection is bound)
+                        a.A_off16, a.A_rowfirst, a.A_rl = _ptr(pj[0]), _ptr(pj[1]), pj[2]
+                        a.P_win, a.P_nspan, a.P_navn = _ptr(pj[3]), pj[4], pj[5]
+                        self.pcr_L = L_pcr
+                        if want_fp:
+                            self.fp_tabs = pj
+                            self.r_where = torch.zeros(1, dtype=torch.int32, device=dev)
+                            a.r_where = _ptr(self.r_where)
+                            if arm:              # (a loop object built directly: on from the start)
+                                self.arm_fused_projection()
+                        if res_ok:
                             self.proj_tabs = pj
-                            a.A_off16, a.A_rowfirst, a.A_rl = _ptr(pj[0]), _ptr(pj[1]), pj[2]
-                            a.P_win, a.P_nspan, a.P_navn = _ptr(pj[3]), pj[4], pj[5]
-                            self.pcr_L = L_pcr
                             words = int(lib.ipx_cg_resident_ll_words(geo[1], pj[6]))
                             self.ll = torch.zeros(words, dtype=torch.int64, device=dev)
                             self.ll_seq = ctypes.c_int64(0)
@@ -894,6 +986,7 @@ def _projected_cg(H, c, Z, Y, b, trust_radius, lb, ub, tol, max_iter, max_infeas
             # ... and the call's first batch behind it (the host's way from here to its own
             # ipx_cg_iterate call is ~50 us of idle GPU otherwise)
             first_end = min(max_iter, batch if batch else _first_batch(max_iter, False))
+            L.arm_fused_projection(first_end)
             b_rows = None if b_zero else P.rows_in(b)      # (the projector's row order)
             # (correction steps of the two projections on the device when the last primings on
             # these patterns needed them or came close: _STEP_PRIMED)
@@ -948,6 +1041,8 @@ def _projected_cg(H, c, Z, Y, b, trust_radius, lb, ub, tol, max_iter, max_infeas
     if np.isinf(trust_radius) and trust_radius > 0 and not has_box \
             and not _hip.debug_form("keep-xn2"):
         L.args.no_radius = 1
+    L.arm_fused_projection(min(max_iter, batch if batch
+                                else _first_batch(max_iter, L.operator is not None)))
     st = stream_ptr()
     L.x.copy_(x0.t)
     L.r.copy_(r0.t)
@@ -991,6 +1086,7 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
         batch_cap = 64 if L.operator is None else 8   # (an operator is applied once per
                                                       #  enqueued iteration, stopped or not)
         carry_at = None          # where a batch on the separate launches ended without a stop
+        settled = True           # the last batch ended with stop code 0 (or none has run)
 
         def iterate(self, it, end):
             self.last = (it, end)
@@ -1004,6 +1100,10 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
                     return
                 raise _hip.IpxError("device loop: the batch enqueued with the priming %r is not "
                                     "the one the driver asks for %r" % (done, (it, end)))
+            if not L.args.fused_proj and self.settled:
+                # (a long solve that began with short batches on a new Jacobian: from the first
+                # batch that pays for the copy of A on, two launches per iteration)
+                L.arm_fused_projection(end - it)
             if L.operator is None:
                 L.args.xsums_carry = 1 if carry else 0
                 try:
@@ -1023,6 +1123,7 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
                 s, pending[0] = list(pending[0]), None
             else:
                 s = dv.read_doubles(L.state, L.state.numel())
+            self.settled = int(s[ST_STOP]) == 0
             if mine and int(s[ST_STOP]) == 0 and not L.args.resident and L.xsums is not None:
                 self.carry_at = self.last[1]
             if fast and int(s[ST_STOP]) == 9:

@@ -700,10 +700,13 @@ class FusedShardedCG:
         # (the rank-local loop keeps the separate launches: the own-range partial sums of
         # ipx_cg_shard2_segment follow their workgroups / row tiles)
         # (resident=None: the tables of the resident kernel are built when the local problem
-        # qualifies; whether the GROUP runs it is decided below)
+        # qualifies; whether the GROUP runs it is decided below.  fused_projection=False: that
+        # form is one GPU's -- its partials follow the solve's workgroups, not the own ranges,
+        # and it leaves g in r_next on alternate iterations -- whatever the local size)
         self.L = L = cg_fused._Loop(H.local, local_P, lb.loc if lb is not None else None,
                                     ub.loc if ub is not None else None,
-                                    resident=None if transport != "dist" else False)
+                                    resident=None if transport != "dist" else False,
+                                    fused_projection=False)
         L.args.resident = 0          # (the single-GPU launch never runs on a rank's local problem)
         a = L.args
         dev = dv.ctx().device

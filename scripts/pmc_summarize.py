@@ -53,11 +53,15 @@ names = {"spmv_A_r": ("k_csr_spmv<false, false, false>",),
          "spmv_H_p": ("k_csr_spmv<true, false, true>",),
          "step1": ("k_cg_step1(",), "step2": ("k_cg_step2(",),
          "step1_spmv_A_r": ("k_cg_step1_ar",), "step2_spmv_H_p": ("k_cg_step2_hp",),
+         "step1_solve_tail": ("k_step1_solve_tail",),
          "banded_solve_with_residual": ("k_solve_decoupled",),
          "banded_solve_pcr": ("k_solve_pcr",)}
 for label, keys in names.items():
     if not any(all(s_ in k for s_ in keys) for k in fetch):
         continue                      # kernel not in this build's loop (fused / unfused)
+    if label in ("step1_spmv_A_r", "banded_solve_pcr") and any("k_step1_solve_tail" in k for k in fetch):
+        continue                      # (the fused projection ran in their place: what is left of
+                                      #  k_solve_pcr are the set-up's plain solves, not the loop's)
     fv, wv = find(fetch, *keys), find(write, *keys)
     # launches of the loop only: the modal size class (priming launches differ)
     f_kb = sorted(fv)[len(fv) // 2]
