@@ -508,9 +508,39 @@ typedef struct ipx_pcg_args {
    * -1 = padding), z = m doubles (M^-1 r), part3 = nblk / 8 + 1 doubles; dinv is then all zero. */
   const double *binv; const int32_t *border; int64_t nblk;
   double *z, *part3;
+  /* coarse level of the two-level preconditioner M^-1 = B^-1 + P X P' (B the blocks above, the
+   * columns of P the indicator vectors of groups of consecutive blocks, X = (P' A A' P)^-1), or
+   * NULL / 0 for the blocks alone: rsum = nblk doubles (the residual summed per block),
+   * coarse_of = m group indices, goff = ncoarse + 1 block offsets of the groups, X = ncoarse x
+   * ncoarse at leading dimension ldx (ncoarse <= ipx_pcg_coarse_max()), y = ncoarse doubles
+   * (X P'r), partc = ipx_pcg_coarse_grid(ncoarse) doubles. */
+  double *rsum; const int32_t *coarse_of, *goff; int64_t ncoarse;
+  const double *X; int64_t ldx;
+  double *y, *partc;
 } ipx_pcg_args;
 int ipx_pcg_state_size(void);
 int ipx_pcg_iterate(const ipx_pcg_args *a, int32_t it_begin, int32_t it_end, void *stream);
+int ipx_pcg_coarse_max(void);
+int ipx_pcg_coarse_grid(int64_t ncoarse);
+/* z = M^-1 r of the two-level preconditioner described by `a` (binv ... partc; z and r are the
+ * arguments, not a->z / a->r) and *rz (device) = r'z, on their own: the first direction of a
+ * solve.  Three launches, no-ops when a->state[6] != 0. */
+int ipx_pcg_precond_apply(const ipx_pcg_args *a, const double *r, double *z, double *rz,
+                          void *stream);
+/* Values of C = P'A into the CSR pattern (C_rowptr, C_colidx: per coarse row the sorted union of
+ * its member rows' columns): coarse row J = the rows order[32 goff[J]] ... order[32 goff[J+1] - 1]
+ * (-1: padding), summed in that order; A's rows have sorted columns. */
+int ipx_csr_aggregate_rows(int64_t ncoarse, const int32_t *A_rowptr, const int32_t *A_colidx,
+                           const double *A_val, const int32_t *order, const int32_t *goff,
+                           const int32_t *C_rowptr, const int32_t *C_colidx, double *C_val,
+                           void *stream);
+/* Greedy aggregation of the graph of a symmetric pattern S (CSR, n rows, sorted columns), host
+ * only: seeds in index order; an aggregate starts as [seed], its member list is walked from the
+ * head, every unassigned neighbour of a member (in the column order of its row) is appended and
+ * assigned at once while the aggregate has fewer than `cap` members.  agg[i] <- aggregate of row
+ * i; returns the number of aggregates, or IPX_EINVAL. */
+int ipx_aggregate_greedy(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t cap,
+                         int32_t *agg);
 int ipx_blockjacobi_build(int64_t nblk, const int32_t *rowptr, const int32_t *colidx,
                           const double *val, const int32_t *order, double *binv, int *flag,
                           void *stream);

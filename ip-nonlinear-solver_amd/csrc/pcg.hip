@@ -7,7 +7,13 @@
 //   Sp = A t, partials of p'Sp                  (CSR SpMV, fused epilogue)
 //   k_pcg_update     alpha = rz / p'Sp;  v += alpha p;  r -= alpha Sp;  partials of ||r||^2, r'z
 //   [k_pcg_block     z = M^-1 r, partials of r'z        (block-Jacobi preconditioner only)]
+//   [k_pcg_coarse    y = X P'r, partials of (P'r)'y     (two-level preconditioner only)]
 //   k_pcg_direction  convergence / stall tests;  beta = rz_next / rz;  p = M^-1 r + beta p
+//
+// Two-level preconditioner (opt-in): M^-1 = B^-1 + P X P', B the 32-row blocks taken over
+// aggregates of the graph of A A' (ipx_aggregate_greedy), the columns of P the indicator vectors
+// of groups of whole blocks, X = (P' A A' P)^-1 = (C C')^-1 with C = P'A (ipx_csr_aggregate_rows)
+// from the dense solver.  A sum of an SPD and a positive semi-definite term: SPD.
 //
 // Preconditioner M: the diagonal of A A' (Jacobi), or -- round 3 -- its diagonal BLOCKS of 32
 // rows taken in a bandwidth-reducing order of the rows (block Jacobi: k_blockjacobi_build forms
@@ -101,10 +107,14 @@ k_blockjacobi_build(const int32_t *__restrict__ rowptr, const int32_t *__restric
 
 // z = M^-1 r for the block-Jacobi M: eight blocks per workgroup, lane (s, blk) forms entry s
 // of its block (the inverse is symmetric: column reads are coalesced); partials of r'z.
+// TWO (two-level form): the residuals of a block being in LDS, their sum in slot order goes to
+// rsum[b] as well -- P'r of the coarse level, whose groups are made of whole blocks.
+template <bool TWO>
 __global__ void __launch_bounds__(PB)
 k_pcg_block(int64_t m, const double *st, const double *__restrict__ r,
             const int32_t *__restrict__ order, const double *__restrict__ binv,
-            double *__restrict__ z, double *__restrict__ p3, int nblk) {
+            double *__restrict__ z, double *__restrict__ p3, int nblk,
+            double *__restrict__ rsum) {
   __shared__ double rb[PB];
   __shared__ double lds[PB / IPX_WAVE];
   if (st[PS_DONE] != 0.0) return;
@@ -115,7 +125,20 @@ k_pcg_block(int64_t m, const double *st, const double *__restrict__ r,
   rb[tid] = rv;
   __syncthreads();
   double acc = 0.0;
-  if (row >= 0) {
+  if constexpr (TWO) {
+    if (b < nblk) {                                            // (padding lanes too: the sum)
+      const double *X = binv + (int64_t)b * BJ * BJ + sl;
+      double rs = 0.0;
+#pragma unroll 8
+      for (int k = 0; k < BJ; ++k) {
+        const double rk = rb[lb * BJ + k];
+        acc += X[k * BJ] * rk;
+        rs += rk;
+      }
+      if (row >= 0) z[row] = acc;
+      if (sl == 0) rsum[b] = rs;
+    }
+  } else if (row >= 0) {
     const double *X = binv + (int64_t)b * BJ * BJ + sl;        // column sl = row sl
 #pragma unroll 8
     for (int k = 0; k < BJ; ++k) acc += X[k * BJ] * rb[lb * BJ + k];
@@ -123,6 +146,135 @@ k_pcg_block(int64_t m, const double *st, const double *__restrict__ r,
   }
   const double tot = ipx_block_reduce<IPX_SUM>(row >= 0 ? rv * acc : 0.0, lds);
   if (tid == 0) p3[blockIdx.x] = tot;
+}
+
+// The coarse level of the two-level preconditioner, y = X P'r with X = (P' A A' P)^-1 explicit
+// (the dense solver's inverse: symmetric, leading dimension ldx) and partials of (P'r)'y, the
+// coarse level's share of r'z.  Every workgroup forms rc = P'r in LDS -- group J's block sums in
+// block order -- and takes CROWS rows of X, a wave RW of them at once: lanes stride the columns,
+// the wave sums them in its fixed order, the partial adds the rows in row order, waves in wave
+// order.
+constexpr int CMAX = 4096;       // coarse rows (rc staged in LDS: 32 KiB)
+constexpr int CROWS = 8;         // rows of X per workgroup
+__global__ void __launch_bounds__(PB)
+k_pcg_coarse(const double *st, const double *__restrict__ rsum, const int32_t *__restrict__ goff,
+             int nc, const double *__restrict__ X, int64_t ldx, double *__restrict__ y,
+             double *__restrict__ pc) {
+  __shared__ double rc[CMAX];
+  __shared__ double wsum[PB / IPX_WAVE];
+  if (st[PS_DONE] != 0.0) return;
+  const int tid = threadIdx.x, lane = tid & (IPX_WAVE - 1), wave = tid / IPX_WAVE;
+  {
+    // a lane's CMAX / PB groups together: their offsets, then round k adds block k of each
+    // (every round's loads are independent; a loop group by group would pay one memory
+    // latency per group and block).  Same order per group: its blocks in block order.
+    constexpr int GU = CMAX / PB;
+    int lo[GU], len[GU], most = 0;
+    double s[GU];
+#pragma unroll
+    for (int u = 0; u < GU; ++u) {
+      const int J = min(tid + u * PB, nc - 1);
+      lo[u] = goff[J];
+      len[u] = tid + u * PB < nc ? goff[J + 1] - lo[u] : 0;
+      s[u] = 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < GU; ++u) most = max(most, len[u]);
+    for (int k = 0; k < most; ++k) {
+      double t[GU];
+#pragma unroll
+      for (int u = 0; u < GU; ++u) t[u] = rsum[lo[u] + min(k, max(len[u] - 1, 0))];
+#pragma unroll
+      for (int u = 0; u < GU; ++u) s[u] += k < len[u] ? t[u] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < GU; ++u)
+      if (tid + u * PB < nc) rc[tid + u * PB] = s[u];
+  }
+  __syncthreads();
+  constexpr int RW = CROWS / (PB / IPX_WAVE);
+  const int r0 = blockIdx.x * CROWS + wave * RW;
+  const double *Xr[RW];
+  double acc[RW];
+#pragma unroll
+  for (int u = 0; u < RW; ++u) {
+    Xr[u] = X + (int64_t)min(r0 + u, nc - 1) * ldx;            // (rows past the end: not stored)
+    acc[u] = 0.0;
+  }
+  constexpr int CU = 4;            // column rounds in flight per lane (clamped loads, zero weight)
+  for (int j0 = lane; j0 < nc; j0 += CU * IPX_WAVE) {
+    double x[CU][RW], rj[CU];
+#pragma unroll
+    for (int q = 0; q < CU; ++q) {
+      const int j = j0 + q * IPX_WAVE, jc = min(j, nc - 1);
+      rj[q] = j < nc ? rc[jc] : 0.0;
+#pragma unroll
+      for (int u = 0; u < RW; ++u) x[q][u] = Xr[u][jc];
+    }
+#pragma unroll
+    for (int q = 0; q < CU; ++q)
+#pragma unroll
+      for (int u = 0; u < RW; ++u) acc[u] += x[q][u] * rj[q];
+  }
+  double part = 0.0;
+#pragma unroll
+  for (int u = 0; u < RW; ++u) {
+    const double yu = ipx_wave_sum(acc[u]);
+    const int row = r0 + u;
+    if (row < nc) {
+      if (lane == 0) y[row] = yu;
+      part += rc[row] * yu;
+    }
+  }
+  if (lane == 0) wsum[wave] = part;
+  __syncthreads();
+  if (tid == 0) pc[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// Two-level z on its own (ipx_pcg_precond_apply): z += P y; workgroup 0 leaves r'z = the block
+// partials + the coarse partials in *rz.
+__global__ void __launch_bounds__(PB)
+k_pcg_coarse_add(int64_t m, const double *st, double *__restrict__ z,
+                 const double *__restrict__ y, const int32_t *__restrict__ coarse_of,
+                 const double *__restrict__ p3, int np3, const double *__restrict__ pc, int npc,
+                 double *__restrict__ rz) {
+  __shared__ double lds[PB / IPX_WAVE];
+  if (st[PS_DONE] != 0.0) return;
+  for (int64_t i = (int64_t)blockIdx.x * PB + threadIdx.x; i < m; i += (int64_t)gridDim.x * PB)
+    z[i] += y[coarse_of[i]];
+  if (blockIdx.x == 0) {
+    const double s3 = ipx_sum_partials<IPX_SUM>(p3, np3, lds);
+    const double sc = ipx_sum_partials<IPX_SUM>(pc, npc, lds);
+    if (threadIdx.x == 0) *rz = s3 + sc;
+  }
+}
+
+// C = P'A, one workgroup per coarse row, a lane per entry of the row: the entry's column is
+// looked up in every member row (binary search; sorted columns), members in slot order.
+__global__ void __launch_bounds__(PB)
+k_csr_aggregate_rows(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
+                     const double *__restrict__ val, const int32_t *__restrict__ order,
+                     const int32_t *__restrict__ goff, const int32_t *__restrict__ crowptr,
+                     const int32_t *__restrict__ ccolidx, double *__restrict__ cval) {
+  const int J = blockIdx.x;
+  const int s0 = goff[J] * BJ, s1 = goff[J + 1] * BJ;
+  for (int e = crowptr[J] + threadIdx.x, ee = crowptr[J + 1]; e < ee; e += PB) {
+    const int col = ccolidx[e];
+    double s = 0.0;
+    for (int t = s0; t < s1; ++t) {
+      const int row = order[t];
+      if (row < 0) continue;
+      const int end = rowptr[row + 1];
+      int lo = rowptr[row], hi = end;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (colidx[mid] < col) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < end && colidx[lo] == col) s += val[lo];
+    }
+    cval[e] = s;
+  }
 }
 
 __global__ void __launch_bounds__(PB)
@@ -168,11 +320,20 @@ k_pcg_update(int64_t m, double *st, int parity, const double *__restrict__ p1, i
   if (threadIdx.x == 0) { p2[c] = out[0]; p2[nchunks + c] = out[1]; }
 }
 
+// what the direction kernel reads of the coarse level (two-level form)
+struct pcg_coarse_view {
+  const double *y;               // X P'r (k_pcg_coarse)
+  const int32_t *coarse_of;      // group of every row
+  const double *pc;              // its partials of (P'r)'y
+  int npc;
+};
+
+template <bool TWO>
 __global__ void __launch_bounds__(PB)
 k_pcg_direction(int64_t m, double *st, int parity, const double *__restrict__ p2, int np2,
                 const double *__restrict__ r, double *p, const double *__restrict__ dinv,
                 int nchunks, const double *__restrict__ z, const double *__restrict__ p3,
-                int np3) {
+                int np3, pcg_coarse_view cv) {
   __shared__ double lds[2 * (PB / IPX_WAVE)];
   const int c = ipx_xcd_item(blockIdx.x, nchunks);
   if (c < 0) return;
@@ -186,6 +347,7 @@ k_pcg_direction(int64_t m, double *st, int parity, const double *__restrict__ p2
   double red[2];
   ipx_sum_partials_multi<2>(parts, counts, lds, red);
   if (z) red[1] = ipx_sum_partials<IPX_SUM>(p3, np3, lds);      // block Jacobi: r'z of k_pcg_block
+  if constexpr (TWO) red[1] += ipx_sum_partials<IPX_SUM>(cv.pc, cv.npc, lds);   // + (P'r)'X P'r
   const double nr = sqrt(red[0]), rz_next = red[1];
   const bool lead = c == 0 && threadIdx.x == 0;
   const double stall_next = nr >= best ? stall + 1.0 : 0.0;
@@ -208,7 +370,10 @@ k_pcg_direction(int64_t m, double *st, int parity, const double *__restrict__ p2
   const double beta = rz_next / rz;
   const int64_t len = (m + nchunks - 1) / nchunks;
   const int64_t lo = (int64_t)c * len, hi = min(m, lo + len);
-  if (z) {
+  if constexpr (TWO) {
+    for (int64_t i = lo + threadIdx.x; i < hi; i += PB)
+      p[i] = (z[i] + cv.y[cv.coarse_of[i]]) + beta * p[i];
+  } else if (z) {
     for (int64_t i = lo + threadIdx.x; i < hi; i += PB) p[i] = z[i] + beta * p[i];
   } else {
     for (int64_t i = lo + threadIdx.x; i < hi; i += PB) p[i] = dinv[i] * r[i] + beta * p[i];
@@ -220,6 +385,17 @@ k_pcg_direction(int64_t m, double *st, int parity, const double *__restrict__ p2
 extern "C" {
 
 int ipx_pcg_state_size(void) { return PS_SIZE; }
+int ipx_pcg_coarse_max(void) { return CMAX; }
+int ipx_pcg_coarse_grid(int64_t ncoarse) {
+  return ncoarse < 1 || ncoarse > CMAX ? IPX_EINVAL : (int)((ncoarse + CROWS - 1) / CROWS);
+}
+
+// the coarse level's fields are all there and within the kernels' limits
+static bool pcg_coarse_ok(const ipx_pcg_args *a) {
+  return a->binv && a->border && a->nblk >= 1 && a->part3 && a->rsum && a->coarse_of && a->goff &&
+         a->X && a->y && a->partc && a->ncoarse >= 1 && a->ncoarse <= CMAX &&
+         a->ncoarse <= a->nblk && a->ldx >= a->ncoarse;
+}
 
 // Enqueue iterations [it_begin, it_end) of the preconditioned CG on A A' v = w.  The caller
 // has set v = 0, r = w, p = D^-1 r and the state block (PS_RZ0 = r'D^-1 r, PS_BEST0 = inf,
@@ -228,6 +404,10 @@ int ipx_pcg_state_size(void) { return PS_SIZE; }
 int ipx_pcg_iterate(const ipx_pcg_args *a, int32_t it_begin, int32_t it_end, void *stream) {
   if (!a || it_end < it_begin || !a->state || !a->part1 || !a->part2 || a->grid < 1)
     return IPX_EINVAL;
+  const bool two = a->X != nullptr;            // two-level: one launch more (k_pcg_coarse)
+  if (two && (!pcg_coarse_ok(a) || !a->z)) return IPX_EINVAL;
+  const int npc = two ? ipx_pcg_coarse_grid(a->ncoarse) : 0;
+  const pcg_coarse_view cv{a->y, a->coarse_of, a->partc, npc};
   hipStream_t st = (hipStream_t)stream;
   const double *guard = a->state + PS_DONE;
   ipx_csr_view A{(int)a->m, (int)a->n, a->A_rowptr, a->A_colidx, a->A_val, a->A_tiles,
@@ -246,16 +426,62 @@ int ipx_pcg_iterate(const ipx_pcg_args *a, int32_t it_begin, int32_t it_end, voi
     IPX_CHECK_LAUNCH();
     const bool block = a->binv != nullptr;
     const int nwg3 = block ? (int)((a->nblk + PB / BJ - 1) / (PB / BJ)) : 0;
+    if (two) {
+      hipLaunchKernelGGL(k_pcg_block<true>, dim3(nwg3), dim3(PB), 0, st, a->m, a->state, a->r,
+                         a->border, a->binv, a->z, a->part3, (int)a->nblk, a->rsum);
+      IPX_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_pcg_coarse, dim3(npc), dim3(PB), 0, st, a->state, a->rsum, a->goff,
+                         (int)a->ncoarse, a->X, a->ldx, a->y, a->partc);
+      IPX_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_pcg_direction<true>, dim3(ipx_xcd_grid(grid)), dim3(PB), 0, st, a->m,
+                         a->state, it & 1, a->part2, grid, a->r, a->p, a->dinv, grid, a->z,
+                         a->part3, nwg3, cv);
+      IPX_CHECK_LAUNCH();
+      continue;
+    }
     if (block) {
-      hipLaunchKernelGGL(k_pcg_block, dim3(nwg3), dim3(PB), 0, st, a->m, a->state, a->r, a->border,
-                         a->binv, a->z, a->part3, (int)a->nblk);
+      hipLaunchKernelGGL(k_pcg_block<false>, dim3(nwg3), dim3(PB), 0, st, a->m, a->state, a->r,
+                         a->border, a->binv, a->z, a->part3, (int)a->nblk, (double *)nullptr);
       IPX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_pcg_direction, dim3(ipx_xcd_grid(grid)), dim3(PB), 0, st, a->m, a->state,
-                       it & 1, a->part2, grid, a->r, a->p, a->dinv, grid,
-                       block ? a->z : (const double *)nullptr, a->part3, nwg3);
+    hipLaunchKernelGGL(k_pcg_direction<false>, dim3(ipx_xcd_grid(grid)), dim3(PB), 0, st, a->m,
+                       a->state, it & 1, a->part2, grid, a->r, a->p, a->dinv, grid,
+                       block ? a->z : (const double *)nullptr, a->part3, nwg3, cv);
     IPX_CHECK_LAUNCH();
   }
+  return IPX_OK;
+}
+
+// z = M^-1 r and *rz = r'z of the two-level preconditioner on their own.
+int ipx_pcg_precond_apply(const ipx_pcg_args *a, const double *r, double *z, double *rz,
+                          void *stream) {
+  if (!a || !r || !z || !rz || !a->state || a->m < 1 || !pcg_coarse_ok(a)) return IPX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int nwg3 = (int)((a->nblk + PB / BJ - 1) / (PB / BJ));
+  const int npc = ipx_pcg_coarse_grid(a->ncoarse);
+  hipLaunchKernelGGL(k_pcg_block<true>, dim3(nwg3), dim3(PB), 0, st, a->m, a->state, r, a->border,
+                     a->binv, z, a->part3, (int)a->nblk, a->rsum);
+  IPX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_pcg_coarse, dim3(npc), dim3(PB), 0, st, a->state, a->rsum, a->goff,
+                     (int)a->ncoarse, a->X, a->ldx, a->y, a->partc);
+  IPX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_pcg_coarse_add, dim3(ipx_grid_for(a->m, PB)), dim3(PB), 0, st, a->m,
+                     a->state, z, a->y, a->coarse_of, a->part3, nwg3, a->partc, npc, rz);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+int ipx_csr_aggregate_rows(int64_t ncoarse, const int32_t *A_rowptr, const int32_t *A_colidx,
+                           const double *A_val, const int32_t *order, const int32_t *goff,
+                           const int32_t *C_rowptr, const int32_t *C_colidx, double *C_val,
+                           void *stream) {
+  if (ncoarse < 1 || !A_rowptr || !A_colidx || !A_val || !order || !goff || !C_rowptr ||
+      !C_colidx || !C_val)
+    return IPX_EINVAL;
+  hipLaunchKernelGGL(k_csr_aggregate_rows, dim3((unsigned)ncoarse), dim3(PB), 0,
+                     (hipStream_t)stream, A_rowptr, A_colidx, A_val, order, goff, C_rowptr,
+                     C_colidx, C_val);
+  IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
 
@@ -278,8 +504,8 @@ int ipx_blockjacobi_apply(int64_t m, int64_t nblk, const int32_t *order, const d
                           void *stream) {
   if (nblk < 1 || !order || !binv || !r || !z || !ws || !state) return IPX_EINVAL;
   const int nwg = (int)((nblk + PB / BJ - 1) / (PB / BJ));
-  hipLaunchKernelGGL(k_pcg_block, dim3(nwg), dim3(PB), 0, (hipStream_t)stream, m, state, r, order,
-                     binv, z, ws, (int)nblk);
+  hipLaunchKernelGGL(k_pcg_block<false>, dim3(nwg), dim3(PB), 0, (hipStream_t)stream, m, state, r,
+                     order, binv, z, ws, (int)nblk, (double *)nullptr);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }

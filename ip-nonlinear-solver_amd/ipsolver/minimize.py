@@ -458,6 +458,11 @@ def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, 
     # anyway, and a non-callable ``hess`` -- finite differences, quasi-Newton -- has no constant
     # value to keep)
     constant_hessian = bool(options.pop("constant_hessian", False))
+    precond = solver_options.current().iterative_precond
+    if precond != "block" and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("iterative_precond=%r: the row-sharded backend builds its own "
+                                  "(A A')^-1 solvers; the option is available on one GPU only"
+                                  % (precond,))
     if _qn.is_strategy(hess) and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "

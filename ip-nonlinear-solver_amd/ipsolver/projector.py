@@ -39,7 +39,9 @@ from .device_mode import RowSelection
 # their names stay public here.
 from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link_rows,  # noqa: F401
                              wide_band_policy, border_columns_limit, link_rows_limit,
-                             check_wide_band, check_border_columns, check_link_rows)
+                             check_wide_band, check_border_columns, check_link_rows,
+                             ITERATIVE_PRECONDS, iterative_precond, iterative_precond_choice,
+                             check_iterative_precond)
 from .banded import (BandedNormalSolver, BandedNotDecoupled, HANDLE_STATS, _Symbolic,  # noqa: F401
                      _SYMBOLIC_ATTR, _symbolic_for, half_bandwidth_of_aat)
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: F401

@@ -10,9 +10,14 @@ bandwidth -- "iterative" (default): the dense Cholesky while it fits, else the p
 rest is banded / block tridiagonal in ``A A'`` (bordered.py).  ``link_rows``: likewise up to this
 many rows (linked.py).  0, the default of both: off, every path as without the option.
 
+``iterative_precond``: the preconditioner of every ``IterativeNormalSolver`` (iterative.py) that
+is built without an explicit one -- "block" (default), "compact" or "two-level".  It is held
+beside the three fields above, which stay the tuple: ``key()`` appends it only when it is not the
+default, so the keys of every setting that existed before it are what they were.
+
 Scoped: ``with scoped(wide_band="block-tridiagonal", link_rows=4): ...`` holds any subset for the
 duration of the block.  ``current().key()`` is part of the key of every cached factorization: a
-new option is a new field here and nowhere else.
+new option is a new name here (``NAMES``, ``check``, ``key``) and nowhere else.
 """
 import collections
 import contextlib
@@ -22,14 +27,28 @@ import numpy as np
 from . import _hip
 
 WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide")
+ITERATIVE_PRECONDS = ("block", "compact", "two-level")
+NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond")
 
 
 class Options(collections.namedtuple("Options", "wide_band border_columns link_rows")):
-    __slots__ = ()
+    iterative_precond = ITERATIVE_PRECONDS[0]      # (an attribute beside the tuple's fields)
+
+    def __new__(cls, wide_band, border_columns, link_rows, iterative_precond="block"):
+        self = super().__new__(cls, wide_band, border_columns, link_rows)
+        self.iterative_precond = iterative_precond
+        return self
+
+    def _replace(self, **changes):
+        precond = changes.pop("iterative_precond", self.iterative_precond)
+        new = super()._replace(**changes)
+        new.iterative_precond = precond
+        return new
 
     def key(self):
         """What tells two settings apart in a cache key."""
-        return tuple(self)
+        extra = () if self.iterative_precond == ITERATIVE_PRECONDS[0] else (self.iterative_precond,)
+        return tuple(self) + extra
 
 
 _current = [Options("iterative", 0, 0)]
@@ -45,6 +64,11 @@ def check(name, value):
         if value not in WIDE_BAND_POLICIES:
             raise ValueError("wide_band must be one of %s, not %r"
                              % (", ".join(repr(p) for p in WIDE_BAND_POLICIES), value))
+        return value
+    if name == "iterative_precond":
+        if value not in ITERATIVE_PRECONDS:
+            raise ValueError("iterative_precond must be one of %s, not %r"
+                             % (", ".join(repr(p) for p in ITERATIVE_PRECONDS), value))
         return value
     if name not in Options._fields:
         raise ValueError("unknown solver option %r" % (name,))
@@ -70,7 +94,7 @@ def pop_from(options):
     """The solver options of a user's ``options`` dict, checked and taken out of it (an option
     that is not given: the value in force), as the keywords of ``scoped``."""
     return {name: check(name, options.pop(name, getattr(current(), name)))
-            for name in Options._fields}
+            for name in NAMES}
 
 
 def _wrappers(name):
@@ -90,3 +114,5 @@ def _wrappers(name):
 wide_band, wide_band_policy, check_wide_band = _wrappers("wide_band")
 border_columns, border_columns_limit, check_border_columns = _wrappers("border_columns")
 link_rows, link_rows_limit, check_link_rows = _wrappers("link_rows")
+iterative_precond, iterative_precond_choice, check_iterative_precond = \
+    _wrappers("iterative_precond")
