@@ -1060,6 +1060,86 @@ int ipx_link_apply(int64_t m, int32_t q, const double *Y, const double *L, const
                    const double *u, const double *w, const int32_t *b_rows, const int32_t *d_rows,
                    double *v, void *stream);
 
+/* ---- sparse direct solve with S = A A' for any pattern (csrc/nested_order.hip, csrc/nested.hip):
+ * nested dissection, a supernodal multifrontal Cholesky factorization, level by level.
+ *
+ * Host graph work (no device call).  The pattern of S is symmetric CSR with sorted columns.
+ * ipx_nd_order: a part (ascending rows) of at most `leaf` rows is one supernode.  A larger part
+ * that is not connected goes piece by piece, the pieces in the order of their lowest rows.  A
+ * connected part larger than `leaf`: breadth-first levels from its lowest row, restarted twice
+ * from the lowest row of the last level; fewer than three levels: one supernode; else the
+ * separator is the first level at which the cumulative count reaches half the part (rounded up),
+ * clamped to 1 ... levels - 2; the rows before it are ordered first, then the rows after it, then
+ * the separator as one supernode.  Rows inside a supernode ascend.  perm (n): position -> row;
+ * sn_ptr (n + 1 slots, count + 1 used): the supernodes' ranges of positions.  Returns the number
+ * of supernodes. */
+int ipx_nd_order(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t leaf,
+                 int32_t *perm, int32_t *sn_ptr);
+/* ipx_nd_symbolic: per supernode its boundary -- the later positions it couples to after fill,
+ * ascending, bnd[bnd_ptr[j] .. bnd_ptr[j + 1]) --, its parent in the elimination tree (the owner
+ * of the first boundary position; -1: a root), its level (0 without children, else one more than
+ * the highest child's; children are the supernodes j' < j with parent j, ascending) and, beside
+ * every boundary position, its index in the parent's front (the parent's own positions, then its
+ * boundary): cmap.  Returns the total boundary length; bnd and cmap are filled only when they
+ * are given and `cap` holds it (call once with bnd = NULL for the size). */
+int64_t ipx_nd_symbolic(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t nsuper,
+                        const int32_t *perm, const int32_t *sn_ptr, int32_t *parent,
+                        int32_t *level, int64_t *bnd_ptr, int32_t *bnd, int32_t *cmap,
+                        int64_t cap);
+
+/* Device side.  A front is the square matrix over a supernode's s own rows and its b boundary
+ * rows, stored ROW-major with leading dimension ld, lower triangle: after the factorization
+ * rows 0 .. s - 1 hold L11, the boundary rows (from row s + pad on) hold L21 in columns
+ * 0 .. s - 1 and the update matrix F22 - L21 L21' behind them; above the diagonal, rows
+ * 0 .. s - 1 hold the same columns of L once more (L' -- what the forward solve reads).  A front of at most
+ * ipx_nd_small_max() rows may be "small": ld = s + b, pad = 0, factored by one workgroup out of
+ * LDS.  Any front may be "large": the own rows padded to a multiple of 64 by unit diagonal
+ * (pad), ld the next multiple of 64 of s + pad + b, factored by 64 x 64 tiles
+ * (ipx_chol_factor_steps).  sn: IPX_ND_FIELDS int64 per supernode --
+ *   0 first position   1 s   2 b   3 offset of its boundary in bnd_rows / cmap / upd
+ *   4 offset of its front in `fronts`   5 ld   6 pad   7, 8 its children: child_idx[7 .. 8)
+ *   9 offset of its ld + 1 doubles in `work` (large fronts)
+ * lists: supernode numbers, a launch takes lists[off .. off + cnt).  perm / bnd_rows: the ROW of
+ * A behind an own / a boundary index.  No floating-point atomics, every sum in a fixed order: the
+ * same values give the same bits. */
+#define IPX_ND_FIELDS 12
+typedef struct {
+  int64_t m, nsuper;
+  const int64_t *sn;
+  const int32_t *perm, *bnd_rows, *cmap, *child_idx, *lists;
+  const int32_t *A_rowptr, *A_colidx;
+  const double *A_val;
+  double *fronts, *work, *y, *upd;
+  int32_t *flag;
+} ipx_nd_args;
+int ipx_nd_small_max(void);
+/* Small fronts of one level, a workgroup each: the entries of S from the rows of A (merge of two
+ * sorted rows, in storage order), the children's updates added through cmap child after child,
+ * the partial Cholesky of the s own columns.  flag: bit 0 -- a pivot fell below 2^-43 of its
+ * diagonal entry of S; bit 2 (with bit 0) -- a pivot was <= 0.  fmax: the largest front of the
+ * list (sizes the LDS).  assemble_only != 0 (either path): the fronts are left as assembled, not
+ * factored -- what the tests compare with S. */
+int ipx_nd_factor_small(const ipx_nd_args *a, int64_t off, int64_t cnt, int32_t fmax,
+                        int32_t assemble_only, void *stream);
+/* Large fronts of one level: assembly, the children's updates (one launch per child ordinal),
+ * then per front s / 64 (rounded up) tile-column steps.  sn_host: the table `sn` in host memory.
+ * Same flag bits. */
+int ipx_nd_factor_large(const ipx_nd_args *a, const int64_t *sn_host, const int32_t *lists_host,
+                        int64_t off, int64_t cnt, int32_t assemble_only, void *stream);
+/* v = (A A')^-1 w in the caller's row order, a launch per level upwards and one downwards, a
+ * workgroup per front.  Upwards: x = [w[own rows]; 0] + the children's update vectors (child
+ * order), L11 y = x1 -> y[positions], upd[boundary] = x2 - L21 y.  Downwards: L11' x1 = y - L21'
+ * x[boundary rows], x[own rows] = x1.  levels_host: per level (offset into lists, number of
+ * fronts, the largest front -- it sizes the LDS, at most 4096). */
+int ipx_nd_solve(const ipx_nd_args *a, int32_t nlevels, const int64_t *levels_host, const double *w,
+                 double *x, void *stream);
+/* `steps` tile-column steps of ipx_chol_factor (M a multiple of 64, steps <= M / 64): the
+ * leading 64 * steps columns hold L, the rest the Schur complement (lower triangle).  work (M + 1
+ * doubles) is the caller's: work[i] the diagonal entry pivot i is judged against, work[M] a
+ * running minimum of pivot / entry.  flag is not cleared; bits as ipx_chol_factor's. */
+int ipx_chol_factor_steps(int64_t M, double *G, int64_t steps, int *flag, double *work,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -855,6 +855,29 @@ int ipx_chol_factor(int64_t M, double *G, int *flag, double *work, void *stream)
   return IPX_OK;
 }
 
+// The first `steps` tile columns of the loop above on a matrix whose `work` the caller has filled
+// (a front of the multifrontal factorization, csrc/nested.hip): L in those columns, the Schur
+// complement behind them.  The flag is the caller's too (not cleared).
+int ipx_chol_factor_steps(int64_t M, double *G, int64_t steps, int *flag, double *work,
+                          void *stream) {
+  if (M < FB || M % FB || steps < 0 || steps > M / FB || !G || !flag || !work) return IPX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = (int)(M / FB);
+  for (int k = 0; k < (int)steps; ++k) {
+    hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(IPX_BLOCK), 0, st, G, (int)M, k, flag, work);
+    IPX_CHECK_LAUNCH();
+    const int rest = nb - k - 1;
+    if (rest > 0) {
+      hipLaunchKernelGGL(k_trsm64, dim3(rest), dim3(IPX_BLOCK), 0, st, G, (int)M, k);
+      IPX_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_syrk64, dim3(rest * (rest + 1) / 2), dim3(IPX_BLOCK), 0, st, G, (int)M,
+                         k, rest);
+      IPX_CHECK_LAUNCH();
+    }
+  }
+  return IPX_OK;
+}
+
 // X (M x M) <- (L L')^-1 from the factor in the lower triangle of G.  G is used as the
 // workspace of the triangular inverse: on return its lower triangle holds L^-1.
 int ipx_chol_inverse(int64_t M, double *G, double *X, void *stream) {

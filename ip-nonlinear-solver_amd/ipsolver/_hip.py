@@ -160,6 +160,12 @@ _SIGNATURES = {
     "ipx_link_spmm": [_I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P],
     "ipx_link_chol": [_I64, _I32, _P, _P, _P, _P, _P, _P],
     "ipx_link_apply": [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ipx_nd_order": [_I64, _P, _P, _I32, _P, _P],
+    "ipx_nd_small_max": [],
+    "ipx_nd_factor_small": [_P, _I64, _I64, _I32, _I32, _P],
+    "ipx_nd_factor_large": [_P, _P, _P, _I64, _I64, _I32, _P],
+    "ipx_nd_solve": [_P, _I32, _P, _P, _P, _P],
+    "ipx_chol_factor_steps": [_I64, _P, _I64, _P, _P, _P],
     "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                             _I32, _P, _P],
 }
@@ -176,8 +182,9 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_lowrank_middle_host": None, "ipx_fd_steps_host": None,
              "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None,
              "ipx_fd_assemble_sym_host": None, "ipx_blocktri_ws_doubles": _I64,
-             "ipx_blockwide_ws_doubles": _I64}
+             "ipx_blockwide_ws_doubles": _I64, "ipx_nd_symbolic": _I64}
 _EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
+                   "ipx_nd_symbolic": [_I64, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64],
                    "ipx_blockwide_ws_doubles": [_I64, _I32],
                    "ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],
                    "ipx_dense_padded": [_I64], "ipx_gram_ws_doubles": [_I64, _I32],

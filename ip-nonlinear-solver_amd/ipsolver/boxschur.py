@@ -30,6 +30,7 @@ from .device import DVec, _p, stream_ptr, ctx
 from .device_mode import RowSelection
 from .iterative import IterativeNormalSolver
 from .linked import link_solver
+from .nested import nested_dissection_solver
 
 _F64 = torch.float64
 
@@ -220,6 +221,9 @@ class BoxSchurNormalSolver:
             mR = B.shape[0]
             # (the wide-band policy: block cyclic reduction when asked for)
             self.inner = wide_band_inner(B)
+            if self.inner is None:
+                # (the option sparse_direct: nested dissection; a refusal leaves the choice below)
+                self.inner = nested_dissection_solver(B)
             if self.inner is None:
                 self.inner = DenseNormalSolver(B) \
                     if mR <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE else IterativeNormalSolver(B)

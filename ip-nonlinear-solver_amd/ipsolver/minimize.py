@@ -463,6 +463,11 @@ def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, 
         raise NotImplementedError("iterative_precond=%r: the row-sharded backend builds its own "
                                   "(A A')^-1 solvers; the option is available on one GPU only"
                                   % (precond,))
+    direct = solver_options.current().sparse_direct
+    if direct != "off" and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("sparse_direct=%r: the row-sharded backend builds its own "
+                                  "(A A')^-1 solvers; the option is available on one GPU only"
+                                  % (direct,))
     if _qn.is_strategy(hess) and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "

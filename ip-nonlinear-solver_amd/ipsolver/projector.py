@@ -34,19 +34,22 @@ from .device import DVec, DeviceCSR, _p, stream_ptr, ctx
 from .dense import DenseNormalSolver, DeviceDense
 from .device_mode import RowSelection
 # The solvers, their selection and its options live in modules of their own, layered
-#   solver_options < banded < blocktri, blockwide, iterative < band_solver < bordered < linked
-#   < boxschur < selection < this one;
+#   solver_options < banded < blocktri, blockwide, iterative, nested < band_solver < bordered
+#   < linked < boxschur < selection < this one;
 # their names stay public here.
 from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link_rows,  # noqa: F401
                              wide_band_policy, border_columns_limit, link_rows_limit,
                              check_wide_band, check_border_columns, check_link_rows,
                              ITERATIVE_PRECONDS, iterative_precond, iterative_precond_choice,
-                             check_iterative_precond)
+                             check_iterative_precond, SPARSE_DIRECT, sparse_direct,
+                             sparse_direct_choice, check_sparse_direct)
 from .banded import (BandedNormalSolver, BandedNotDecoupled, HANDLE_STATS, _Symbolic,  # noqa: F401
                      _SYMBOLIC_ATTR, _symbolic_for, half_bandwidth_of_aat)
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: F401
 from .blockwide import WideBlockTridiagonalNormalSolver  # noqa: F401
 from .iterative import IterativeNormalSolver, PcgArgs  # noqa: F401
+from .nested import (NestedDissectionNormalSolver, NestedDissectionRefused,  # noqa: F401
+                     nested_dissection_solver)
 from .band_solver import border_reach, direct_band_solver, direct_solver_class  # noqa: F401
 from .bordered import (BorderedNormalSolver, BorderedRefused, border_split,  # noqa: F401
                        bordered_solver, _border_split_for)

@@ -13,6 +13,7 @@ from .boxschur import BoxSchurNormalSolver, analysis_for, general_rows_pattern
 from .dense import DenseNormalSolver, DeviceDense
 from .iterative import IterativeNormalSolver
 from .linked import LinkedRowsNormalSolver, _link_split_for, link_solver
+from .nested import nested_dissection_solver
 from .solver_options import current
 
 _last_solver = [None]
@@ -151,6 +152,15 @@ def _rule_wide_band(A, f, deferred):
         return direct_band_solver(A)
 
 
+def _rule_sparse_direct(A, f, deferred):
+    """Under the option sparse_direct: the nested-dissection multifrontal Cholesky for a matrix no
+    band solver took, of any m.  A matrix with worthwhile box rows stays with the box-Schur
+    elimination below (whose inner choice gets this solver under the option); a matrix past the
+    solver's limits is the next rule's turn."""
+    if not f.box_any:
+        return nested_dissection_solver(A)
+
+
 def _rule_dense(A, f, deferred):
     if A.shape[0] <= DenseNormalSolver.MAX_ROWS_FROM_SPARSE:
         return DenseNormalSolver(A)             # wide band: dense Cholesky of A A'
@@ -171,9 +181,10 @@ def _rule_iterative(A, f, deferred):
 
 
 # (a rule put before ``_rule_banded`` that takes matrices whose A A' a row order makes narrow has to
-# be mirrored in ``_banded_row_order`` below, which predicts the banded rule's turn from the facts)
+# be mirrored in ``_banded_row_order`` below, which predicts the banded rule's turn from the facts;
+# ``_rule_sparse_direct`` sits after ``_rule_banded`` and needs no mirror there)
 RULES = (_rule_link_rows, _rule_border_columns, _rule_barrier_jacobian, _rule_box_over_wide_band,
-         _rule_banded, _rule_box_schur, _rule_wide_band, _rule_dense,
+         _rule_banded, _rule_box_schur, _rule_wide_band, _rule_sparse_direct, _rule_dense,
          _rule_box_schur_any_sparsity, _rule_iterative)
 
 

@@ -15,6 +15,10 @@ is built without an explicit one -- "block" (default), "compact" or "two-level".
 beside the three fields above, which stay the tuple: ``key()`` appends it only when it is not the
 default, so the keys of every setting that existed before it are what they were.
 
+``sparse_direct``: "off" (default), or "nested-dissection": a sparse A that no band solver takes
+and (without the option) the dense Cholesky or the preconditioned CG would, is factored by the
+nested-dissection multifrontal Cholesky (nested.py).  Held and keyed like ``iterative_precond``.
+
 Scoped: ``with scoped(wide_band="block-tridiagonal", link_rows=4): ...`` holds any subset for the
 duration of the block.  ``current().key()`` is part of the key of every cached factorization: a
 new option is a new name here (``NAMES``, ``check``, ``key``) and nowhere else.
@@ -28,26 +32,35 @@ from . import _hip
 
 WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide")
 ITERATIVE_PRECONDS = ("block", "compact", "two-level")
-NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond")
+SPARSE_DIRECT = ("off", "nested-dissection")
+NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond", "sparse_direct")
+# the options held beside the tuple: name -> allowed values, the first the default
+_BESIDE = {"iterative_precond": ITERATIVE_PRECONDS, "sparse_direct": SPARSE_DIRECT}
 
 
 class Options(collections.namedtuple("Options", "wide_band border_columns link_rows")):
-    iterative_precond = ITERATIVE_PRECONDS[0]      # (an attribute beside the tuple's fields)
+    iterative_precond = ITERATIVE_PRECONDS[0]      # (attributes beside the tuple's fields)
+    sparse_direct = SPARSE_DIRECT[0]
 
-    def __new__(cls, wide_band, border_columns, link_rows, iterative_precond="block"):
+    def __new__(cls, wide_band, border_columns, link_rows, iterative_precond="block",
+                sparse_direct="off"):
         self = super().__new__(cls, wide_band, border_columns, link_rows)
         self.iterative_precond = iterative_precond
+        self.sparse_direct = sparse_direct
         return self
 
     def _replace(self, **changes):
-        precond = changes.pop("iterative_precond", self.iterative_precond)
+        beside = {name: changes.pop(name, getattr(self, name)) for name in _BESIDE}
         new = super()._replace(**changes)
-        new.iterative_precond = precond
+        for name, value in beside.items():
+            setattr(new, name, value)
         return new
 
     def key(self):
         """What tells two settings apart in a cache key."""
         extra = () if self.iterative_precond == ITERATIVE_PRECONDS[0] else (self.iterative_precond,)
+        if self.sparse_direct != SPARSE_DIRECT[0]:
+            extra += (self.sparse_direct,)
         return tuple(self) + extra
 
 
@@ -65,10 +78,10 @@ def check(name, value):
             raise ValueError("wide_band must be one of %s, not %r"
                              % (", ".join(repr(p) for p in WIDE_BAND_POLICIES), value))
         return value
-    if name == "iterative_precond":
-        if value not in ITERATIVE_PRECONDS:
-            raise ValueError("iterative_precond must be one of %s, not %r"
-                             % (", ".join(repr(p) for p in ITERATIVE_PRECONDS), value))
+    if name in _BESIDE:
+        if value not in _BESIDE[name]:
+            raise ValueError("%s must be one of %s, not %r"
+                             % (name, ", ".join(repr(p) for p in _BESIDE[name]), value))
         return value
     if name not in Options._fields:
         raise ValueError("unknown solver option %r" % (name,))
@@ -93,8 +106,14 @@ def scoped(**changes):
 def pop_from(options):
     """The solver options of a user's ``options`` dict, checked and taken out of it (an option
     that is not given: the value in force), as the keywords of ``scoped``."""
-    return {name: check(name, options.pop(name, getattr(current(), name)))
-            for name in NAMES}
+    held = {name: check(name, options.pop(name, getattr(current(), name)))
+            for name in NAMES[:4]}
+    # (``sparse_direct`` only when it is given: without it ``scoped`` leaves the value in force
+    # as it is, and the record of a call that does not use it reads as before the option)
+    for name in NAMES[4:]:
+        if name in options:
+            held[name] = check(name, options.pop(name))
+    return held
 
 
 def _wrappers(name):
@@ -116,3 +135,4 @@ border_columns, border_columns_limit, check_border_columns = _wrappers("border_c
 link_rows, link_rows_limit, check_link_rows = _wrappers("link_rows")
 iterative_precond, iterative_precond_choice, check_iterative_precond = \
     _wrappers("iterative_precond")
+sparse_direct, sparse_direct_choice, check_sparse_direct = _wrappers("sparse_direct")
