@@ -419,6 +419,10 @@ typedef struct ipx_cg_args {
    * -- the caller knows that the previous batch on this block ended exactly there without a
    * stop and that nothing has run on it since.  0: that iteration reads x and p. */
   int32_t xsums_carry;
+  /* != 0: entry k of every row of A sits at column A_rowfirst[row] + k (rows are runs of
+   * consecutive columns, as on a banded Jacobian): the fused projection takes the offset as the
+   * constant k and does not read A_ell_off16 (which stays bound).  0: the table is read. */
+  int32_t A_contig;
 } ipx_cg_args;
 /* k_cg_step2_hp mode bits: 1 = no radius / box test, 2 = no orthogonality test (the two
  * ipx_cg_resume and ipx_cg_step2_hp take), 4 = the radius test from the carried sums (set by

@@ -1444,13 +1444,15 @@ __device__ __forceinline__ double pcr_rcp(double b) {
 // decoupling level, and atomics on ONE word serialise in L2 at ~45 ns each -- 71 us of this
 // kernel's 78 at m = 1e5 (1540 waves x 7 levels), half of a refactorization.
 __global__ void __launch_bounds__(IPX_BLOCK)
-k_pcr_check(int m, int rows_wg, const double *__restrict__ band, int *flags) {
+k_pcr_check(int m, int rows_wg, int nwin, const double *__restrict__ band, int *flags) {
   constexpr int PAD = 1 << PCR_LMAX;
   constexpr int RS = PCR_RMAX + 2 * PAD;
   __shared__ double pa[2][RS], pr[2][RS];
+  const int wg = ipx_xcd_item(blockIdx.x, nwin);     // the solve's windows, the solve's placement
+  if (wg < 0) return;
   const int H = 1 << PCR_LMAX;
   const int R = rows_wg + 2 * H;
-  const int64_t g0 = (int64_t)blockIdx.x * rows_wg - H;
+  const int64_t g0 = (int64_t)wg * rows_wg - H;
   const int tid = threadIdx.x;
   double a[PCR_NR], b[PCR_NR], b0[PCR_NR];
   bool own[PCR_NR];
@@ -1554,7 +1556,7 @@ __device__ __forceinline__ void pcr_levels(int L, int R, int tid, double (&a)[NR
 // 9.1 (256) and 8.0 (1024).  One window row per lane, half the tail's loads per lane.
 template <int QV, int NR, bool ROWS, int TB, bool POST = false>
 __global__ void __launch_bounds__(TB)
-k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
+k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band,
             const double *__restrict__ w, double *__restrict__ x, double *__restrict__ partial,
             const double *__restrict__ guard, AtvJob atv, RowsJob rows = RowsJob{},
             PostJob post = PostJob{}) {
@@ -1565,18 +1567,22 @@ k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
   __shared__ double sx[PCR_RMAX];
   __shared__ double red_lds[TB / IPX_WAVE];
   constexpr int RWU = ROWS_PRODUCTS / TB;          // products per lane (ROWS form)
+  // window wg of nwin: neighbouring windows, whose halos are each other's own rows, run on one
+  // XCD (ipx_common.h); a padding workgroup leaves as a whole
+  const int wg = ipx_xcd_item(blockIdx.x, nwin);
+  if (wg < 0) return;
   IPX_STAMP(0);
   // A'v tail: this workgroup's variables -- the FIRST loads of the kernel, so that the tail's
   // own loads (which need them) can be issued while the solve's inputs are still in flight
   int av0 = 0, avn = 0;
   if (QV > 0) {
-    av0 = atv.vown[blockIdx.x];
-    avn = atv.vown[blockIdx.x + 1] - av0;
+    av0 = atv.vown[wg];
+    avn = atv.vown[wg + 1] - av0;
   }
   const double stop = guard ? *guard : 0.0;
   const int H = 1 << L;
   const int R = rows_wg + 2 * H;
-  const int64_t own0 = (int64_t)blockIdx.x * rows_wg;
+  const int64_t own0 = (int64_t)wg * rows_wg;
   const int64_t g0 = own0 - H;                      // global row of window row 0
   const int tid = threadIdx.x;
   // ROWS: the entries of the window's rows, the head of the kernel's only dependent chain
@@ -1663,8 +1669,8 @@ k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
   double pep[POST ? POST_PG : 1], peq[POST ? POST_PG : 1];
   double prc[POST ? POST_PG + 1 : 1], prp[POST ? POST_PG : 1], prq[POST ? POST_PG : 1];
   if constexpr (POST) {
-    pg0 = post.own_g[blockIdx.x]; pgn = post.own_g[blockIdx.x + 1] - pg0;
-    pe0 = post.own_e[blockIdx.x]; pen = post.own_e[blockIdx.x + 1] - pe0;
+    pg0 = post.own_g[wg]; pgn = post.own_g[wg + 1] - pg0;
+    pe0 = post.own_e[wg]; pen = post.own_e[wg + 1] - pe0;
     const ipx_group_tab &T = post.T;
 #pragma unroll
     for (int k = 0; k < POST_PG; ++k) {
@@ -1745,8 +1751,8 @@ k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
     }
     const double gtot = ipx_block_reduce<IPX_SUM>(gacc, red_lds);
     if (tid == 0) {
-      atv.part3[blockIdx.x] = gtot;
-      atv.part3[gridDim.x + blockIdx.x] = 0.0;
+      atv.part3[wg] = gtot;
+      atv.part3[nwin + wg] = 0.0;
     }
     if (!partial) return;
   }
@@ -1808,9 +1814,9 @@ k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
     }
     const double gtot = ipx_block_reduce<IPX_SUM>(acc, red_lds);
     if (tid == 0) {
-      post.part[blockIdx.x] = gtot;
-      post.part[post.count + blockIdx.x] = 0.0;
-      for (int k = blockIdx.x + gridDim.x; k < post.count; k += gridDim.x) {
+      post.part[wg] = gtot;
+      post.part[post.count + wg] = 0.0;
+      for (int k = wg + nwin; k < post.count; k += nwin) {
         post.part[k] = 0.0;
         post.part[post.count + k] = 0.0;
       }
@@ -1839,7 +1845,7 @@ k_solve_pcr(int m, int rows_wg, int L, const double *__restrict__ band,
     }
   }
   const double tot = ipx_block_reduce<IPX_SUM>(acc, red_lds);
-  if (tid == 0) partial[blockIdx.x] = tot;
+  if (tid == 0) partial[wg] = tot;
   IPX_STAMP(7);
 }
 
@@ -1852,11 +1858,12 @@ int launch_solve_pcr_q(const LevDev &lv, int L, const double *w, double *x, doub
   // rows per lane: the window is rows_wg + 2^(L+1) rows
   constexpr int NRL = (PCR_RMAX + PCR_TB - 1) / PCR_TB;
   if (rows_wg + 2 * (1 << L) <= PCR_TB)
-    hipLaunchKernelGGL((k_solve_pcr<QV, 1, false, PCR_TB>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
-                       rows_wg, L, lv.band, w, x, partial, guard, atv, RowsJob{});
+    hipLaunchKernelGGL((k_solve_pcr<QV, 1, false, PCR_TB>), dim3(ipx_xcd_grid(grid)), dim3(PCR_TB),
+                       0, st, lv.m, rows_wg, L, grid, lv.band, w, x, partial, guard, atv, RowsJob{});
   else
-    hipLaunchKernelGGL((k_solve_pcr<QV, NRL, false, PCR_TB>), dim3(grid), dim3(PCR_TB), 0, st,
-                       lv.m, rows_wg, L, lv.band, w, x, partial, guard, atv, RowsJob{});
+    hipLaunchKernelGGL((k_solve_pcr<QV, NRL, false, PCR_TB>), dim3(ipx_xcd_grid(grid)),
+                       dim3(PCR_TB), 0, st, lv.m, rows_wg, L, grid, lv.band, w, x, partial, guard,
+                       atv, RowsJob{});
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
@@ -1889,11 +1896,13 @@ int launch_solve_pcr_rows(const LevDev &lv, int L, const RowsJob &rows, double *
                                 (int)(LDS_LIMIT - 44 * 1024));
       attr_post = true;
     }
-    hipLaunchKernelGGL((k_solve_pcr<0, 1, true, PCR_TB, true>), dim3(grid), dim3(PCR_TB), lds, st,
-                       lv.m, rows_wg, L, lv.band, nullptr, x, partial, guard, AtvJob{}, rows, *post);
+    hipLaunchKernelGGL((k_solve_pcr<0, 1, true, PCR_TB, true>), dim3(ipx_xcd_grid(grid)),
+                       dim3(PCR_TB), lds, st, lv.m, rows_wg, L, grid, lv.band, nullptr, x, partial,
+                       guard, AtvJob{}, rows, *post);
   } else {
-    hipLaunchKernelGGL((k_solve_pcr<0, 1, true, PCR_TB>), dim3(grid), dim3(PCR_TB), lds, st, lv.m,
-                       rows_wg, L, lv.band, nullptr, x, partial, guard, AtvJob{}, rows);
+    hipLaunchKernelGGL((k_solve_pcr<0, 1, true, PCR_TB>), dim3(ipx_xcd_grid(grid)), dim3(PCR_TB),
+                       lds, st, lv.m, rows_wg, L, grid, lv.band, nullptr, x, partial, guard,
+                       AtvJob{}, rows);
   }
   IPX_CHECK_LAUNCH();
   return IPX_OK;
@@ -1936,9 +1945,11 @@ int launch_solve_pcr(const LevDev &lv, int L, const double *w, double *x, double
 // PRIME: the projection alone, for the priming (csrc/cg.hip prime_project_tail): no step -- the
 // span holds r_in itself, no p'Hp fold, no state words read or written, *guard != 0 skips the
 // launch --, g = sign (r_in - A'v) as AtvJob's sign forms it.
-template <int QV, int XN, bool PRIME = false>
+// CONTIG (the job's flag): entry k of every row of A sits at column A_rowfirst[row] + k -- the
+// offset is the constant k, the 16-bit table is not read.
+template <int QV, int XN, bool PRIME = false, bool CONTIG = false>
 __global__ void __launch_bounds__(PCR_TB)
-k_step1_solve_tail(int m, int rows_wg, int L, const double *__restrict__ band,
+k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict__ band,
                    ipx_fused_proj_job J) {
   constexpr int TB = PCR_TB;
   constexpr int PAD = 1 << PCR_LMAX;
@@ -1952,7 +1963,9 @@ k_step1_solve_tail(int m, int rows_wg, int L, const double *__restrict__ band,
   __shared__ double span[IPX_FP_SPAN];
   __shared__ double red_lds[TB / IPX_WAVE];
   __shared__ double fold_lds[FW / IPX_WAVE];
-  const int tid = threadIdx.x, wg = blockIdx.x;
+  // window wg of nwin, placed as k_solve_pcr's: windows w and w + 1 share an XCD's L2
+  const int tid = threadIdx.x, wg = ipx_xcd_item(blockIdx.x, nwin);
+  if (wg < 0) return;
   const int av0 = J.vown[wg], avn = J.vown[wg + 1] - av0;
   const int c_lo = J.win[2 * wg], nspan = J.win[2 * wg + 1] - c_lo;
   static_assert(!PRIME || XN == 1, "the priming's projection forms no radius test");
@@ -1997,7 +2010,7 @@ k_step1_solve_tail(int m, int rows_wg, int L, const double *__restrict__ band,
     av[k] = 0.0; ao[k] = 0;
     if (k < J.rl) {                                   // (uniform)
       av[k] = J.A_ell_val[(int64_t)k * m + gc];
-      ao[k] = (int)J.A_ell_off16[(int64_t)k * m + gc];
+      ao[k] = CONTIG ? k : (int)J.A_ell_off16[(int64_t)k * m + gc];
     }
   }
   double a[1], b[1], d[1];
@@ -2147,13 +2160,13 @@ k_step1_solve_tail(int m, int rows_wg, int L, const double *__restrict__ band,
   const double gtot = ipx_block_reduce<IPX_SUM>(gacc, red_lds);
   if (tid == 0) {
     J.part3[wg] = gtot;
-    J.part3[gridDim.x + wg] = 0.0;
+    J.part3[nwin + wg] = 0.0;
   }
   if constexpr (XN == 0) {
     const double xtot = ipx_block_reduce<IPX_SUM>(xacc, red_lds);
     if (tid == 0) {
       J.part2[wg] = xtot;
-      J.part2[gridDim.x + wg] = 0.0;
+      J.part2[nwin + wg] = 0.0;
     }
   }
   // ---- residual of the own rows (k_solve_pcr's)
@@ -2171,32 +2184,39 @@ k_step1_solve_tail(int m, int rows_wg, int L, const double *__restrict__ band,
   if (tid == 0) J.part4[wg] = tot;
 }
 
-template <int QV>
-int launch_step1_solve_tail_q(const LevDev &lv, int L, const ipx_fused_proj_job &J, int grid,
+template <int QV, bool CONTIG>
+int launch_step1_solve_tail_qc(const LevDev &lv, int L, const ipx_fused_proj_job &J, int nwin,
                               hipStream_t st) {
   const int rows_wg = DEC_CHUNKS * lv.q;
+  const dim3 grid(ipx_xcd_grid(nwin)), block(PCR_TB);
   if (J.prime) {
-    hipLaunchKernelGGL((k_step1_solve_tail<QV, 1, true>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
-                       rows_wg, L, lv.band, J);
+    hipLaunchKernelGGL((k_step1_solve_tail<QV, 1, true, CONTIG>), grid, block, 0, st, lv.m,
+                       rows_wg, L, nwin, lv.band, J);
     IPX_CHECK_LAUNCH();
     return IPX_OK;
   }
   switch (J.xn) {
     case 0:
-      hipLaunchKernelGGL((k_step1_solve_tail<QV, 0>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
-                         rows_wg, L, lv.band, J);
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 0, false, CONTIG>), grid, block, 0, st, lv.m,
+                         rows_wg, L, nwin, lv.band, J);
       break;
     case 1:
-      hipLaunchKernelGGL((k_step1_solve_tail<QV, 1>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
-                         rows_wg, L, lv.band, J);
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 1, false, CONTIG>), grid, block, 0, st, lv.m,
+                         rows_wg, L, nwin, lv.band, J);
       break;
     default:
-      hipLaunchKernelGGL((k_step1_solve_tail<QV, 2>), dim3(grid), dim3(PCR_TB), 0, st, lv.m,
-                         rows_wg, L, lv.band, J);
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 2, false, CONTIG>), grid, block, 0, st, lv.m,
+                         rows_wg, L, nwin, lv.band, J);
       break;
   }
   IPX_CHECK_LAUNCH();
   return IPX_OK;
+}
+template <int QV>
+int launch_step1_solve_tail_q(const LevDev &lv, int L, const ipx_fused_proj_job &J, int nwin,
+                              hipStream_t st) {
+  return J.contig ? launch_step1_solve_tail_qc<QV, true>(lv, L, J, nwin, st)
+                  : launch_step1_solve_tail_qc<QV, false>(lv, L, J, nwin, st);
 }
 
 // variables per lane of the tail at PCR_TB lanes (launch_solve_pcr's count)
@@ -2590,8 +2610,9 @@ int flag_ints(const Banded *h) { return h->pcr_flags ? 1 + 2 * (PCR_LMAX + 1) : 
 int launch_pcr_check(Banded *h, hipStream_t st) {
   // the cyclic reduction of the matrix alone: at which level has it decoupled?
   const Level &l0 = h->lev[0];
-  hipLaunchKernelGGL(k_pcr_check, dim3((l0.P + DEC_CHUNKS - 1) / DEC_CHUNKS), dim3(IPX_BLOCK), 0,
-                     st, l0.m, DEC_CHUNKS * l0.q, l0.band, h->pcr_flags);
+  const int nwin = (l0.P + DEC_CHUNKS - 1) / DEC_CHUNKS;
+  hipLaunchKernelGGL(k_pcr_check, dim3(ipx_xcd_grid(nwin)), dim3(IPX_BLOCK), 0, st, l0.m,
+                     DEC_CHUNKS * l0.q, nwin, l0.band, h->pcr_flags);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }

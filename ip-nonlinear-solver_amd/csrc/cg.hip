@@ -1565,6 +1565,7 @@ int launch_projection_half(const ipx_cg_args *a, const LoopPlan &P, const HalfAr
     J.xs_comp = carried ? a->xsums + 3 * nraw + 1 : nullptr;
     J.ncomp = carried ? P.xs_ncomp : 0; J.it = h.it;
     J.A_ell_val = a->A_ell_val; J.A_ell_off16 = (const uint16_t *)a->A_ell_off16;
+    J.contig = a->A_contig != 0;
     J.A_rowfirst = a->A_rowfirst; J.rl = (int)a->A_rl; J.win = a->P_win; J.n = a->n;
     J.vown = a->At_vown; J.qv = (int)a->At_qv; J.ell_row = a->At_ell_row; J.ell_val = a->At_ell_val;
     J.v = a->v; J.part3 = a->part3; J.part4 = a->part4;
@@ -2329,6 +2330,7 @@ static int prime_project_tail(const ipx_cg_args *a, const LoopPlan &P, const ipx
     ipx_fused_proj_job J{};
     J.r_in = x; J.g_out = z; J.xn = 1; J.prime = 1; J.sign = sign; J.guard = guard;
     J.A_ell_val = a->A_ell_val; J.A_ell_off16 = (const uint16_t *)a->A_ell_off16;
+    J.contig = a->A_contig != 0;
     J.A_rowfirst = a->A_rowfirst; J.rl = (int)a->A_rl; J.win = a->P_win; J.n = a->n;
     J.vown = a->At_vown; J.qv = (int)a->At_qv; J.ell_row = a->At_ell_row; J.ell_val = a->At_ell_val;
     J.v = a->v; J.part3 = pz; J.part4 = pt;

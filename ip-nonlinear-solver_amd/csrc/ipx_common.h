@@ -56,10 +56,14 @@ static inline int ipx_grid_for(int64_t n, int per_block, int cap = IPX_VEC_GRID_
 // ---- XCD-aware work mapping ---------------------------------------------
 // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one), and
 // each XCD has its own 4 MiB L2.  Every kernel of the CG loop therefore maps
-// work item t (row tile, or chunk of vector elements) so that XCD k always
+// work item t (row tile, chunk of vector elements, or window of the cyclic-
+// reduction solve: csrc/banded.hip) so that XCD k always
 // owns the k-th eighth of the index space: the slices of x, p, r, Hp an XCD
 // read or wrote in one kernel are the slices it needs in the next, and can be
-// served from its own L2 instead of the fabric.  Launch ipx_xcd_grid(n) work-
+// served from its own L2 instead of the fabric.  For the solve's windows it also
+// puts neighbours on one XCD: the halo rows of window w are the own rows of
+// windows w - 1 and w + 1, and the lines under them are fetched over the fabric
+// once instead of twice.  Launch ipx_xcd_grid(n) work-
 // groups; ipx_xcd_item returns the item or -1 for the few padding groups.
 static inline int ipx_xcd_grid(int nitems) { return 8 * ((nitems + 7) / 8); }
 // Rounds of IPX_BLOCK items per workgroup (rmin..rmax) for an item-parallel kernel whose items
@@ -712,8 +716,10 @@ struct ipx_fused_proj_job {
   const double *x, *p;            //    workgroup, second half zero); 1: not formed; 2: the first
   double *part2;                  //    xs_ncomp workgroups fold their slice of the carried sums
   const double *xs_raw; int nraw; double *xs_comp; int ncomp; int it;
-  // A in ELL-transposed form (entry k of row i at [k * m + i]; the column as rowfirst[i] + off16)
+  // A in ELL-transposed form (entry k of row i at [k * m + i]; the column as rowfirst[i] + off16;
+  // contig != 0: off16 of entry k is k in every row, the kernel does not read the table)
   const double *A_ell_val; const uint16_t *A_ell_off16; const int32_t *A_rowfirst; int rl;
+  int contig;
   const int32_t *win;             // per workgroup: first / one past the last column of its span
   int64_t n;
   const int32_t *vown; int qv;    // A' (ELL(2)) on the own variables: see AtvJob

@@ -270,9 +270,11 @@ def load():
 #   no-fused-projection  problems beyond the resident kernel's size: step1 + A.r, the solve with
 #                      its tail and step2 + H.p as three launches per iteration instead of the
 #                      projection half as one (csrc/banded.hip k_step1_solve_tail)
+#   table-columns      the fused projection reads the 16-bit column offsets of A even where every
+#                      row is a run of consecutive columns (ipx_cg_args.A_contig stays 0)
 DEBUG_FORMS = ("no-fuse", "no-resident", "no-compact-groups", "no-affine-groups", "keep-xn2",
                "read-xn2", "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop",
-               "no-fused-projection")
+               "no-fused-projection", "table-columns")
 
 
 def debug_form(name):

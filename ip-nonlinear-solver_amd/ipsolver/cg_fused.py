@@ -49,7 +49,7 @@ class CgArgs(ctypes.Structure):
         ("LR_W", _P), ("LR_state", _P), ("LR_part", _P), ("LR_mem", _I64), ("LR_rows", _I64),
         ("xsums", _P),
         ("fused_proj", _I64), ("A_ell_val", _P), ("A_ell_off16", _P), ("r_where", _P),
-        ("xsums_carry", ctypes.c_int32))]
+        ("xsums_carry", ctypes.c_int32), ("A_contig", ctypes.c_int32))]
 
 
 # Counters over the life of the process (diagnostics: how often the device loop
@@ -407,7 +407,8 @@ def ell_transposed(A, rl):
     lane per row, consecutive lanes consecutive rows): ``(off16, val)`` with entry k of row i at
     ``[k * m + i]`` -- the column as a 16-bit offset from the row's first column, the entries in
     their CSR order.  The offsets and the gather map are symbolic (cached on the pattern); the
-    values are one gather per new value array, like ``ell_rows``."""
+    values are one gather per new value array, like ``ell_rows``.  ``ell_contiguous`` says
+    whether the offset of entry k is k in every row (symbolic too)."""
     done = getattr(A, "_ipx_ellt_done", None)          # same matrix object: same values
     if done is not None and done[0] == rl:
         return done[1], done[2]
@@ -423,15 +424,23 @@ def ell_transposed(A, rl):
                + np.arange(rl, dtype=np.int64)[:, None]).ravel()
         assert src.size == 0 or (src.min() >= 0 and src.max() < pat.nnz)
         dev = ctx().device
+        contig = bool(np.array_equal(off, np.broadcast_to(np.arange(rl, dtype=np.int64), off.shape)))
         cache = pat._ipx_ellt = (
             rl, torch.from_numpy(np.ascontiguousarray(off.T).ravel().astype(np.uint16)
                                  .view(np.int16)).to(dev),
-            torch.from_numpy(src.astype(np.int32)).to(dev))
-    _, off16, src = cache
+            torch.from_numpy(src.astype(np.int32)).to(dev), contig)
+    _, off16, src, _ = cache
     val = torch.empty(src.numel(), dtype=torch.float64, device=off16.device)
     _hip.call("ipx_gather", src.numel(), _p(A.val), _p(src), None, None, _p(val), stream_ptr())
     A._ipx_ellt_done = (rl, off16, val)
     return off16, val
+
+
+def ell_contiguous(A, rl):
+    """After ``ell_transposed(A, rl)``: entry k of every row of A sits at the row's first column
+    + k (ipx_cg_args.A_contig: the fused projection then reads no column offsets)."""
+    cache = getattr(A.pattern, "_ipx_ellt", None)
+    return cache is not None and cache[0] == rl and cache[3]
 
 
 def _solver_kind(solver):
@@ -593,6 +602,8 @@ class _Loop:
             return False
         self.A_ell_off16, self.A_ell_val = ell_transposed(A, self.fp_tabs[2])
         a.A_ell_off16, a.A_ell_val = _ptr(self.A_ell_off16), _ptr(self.A_ell_val)
+        a.A_contig = 1 if ell_contiguous(A, self.fp_tabs[2]) \
+            and not _hip.debug_form("table-columns") else 0
         a.fused_proj = 1
         return True
 
