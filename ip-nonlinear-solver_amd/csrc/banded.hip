@@ -21,6 +21,7 @@
 // solve is bitwise reproducible.  A non-positive pivot sets an error flag
 // that ipx_banded_status() reports (rank-deficient Jacobian).
 #include "ipx_common.h"
+#include "pcr_window.h"
 #include <vector>
 
 namespace {
@@ -83,8 +84,6 @@ struct Banded {
                               // ipx_banded_status_deferred assumes for the next one
   std::vector<void *> allocs;
 };
-
-constexpr int PCR_LMAX = 7;     // reduction distance up to 2^7 = 128 rows
 
 __device__ __forceinline__ int chunk_rows(int m, int q, int c, int P, int t) {
   // interior rows of chunk t: all chunks have c rows except the last, which
@@ -625,6 +624,17 @@ constexpr int DOWN_T = 256;          // threads per workgroup in k_down0 (T <= 6
 constexpr int MID_T = 512;
 constexpr int JB = 8;                // recurrence steps per register block
 constexpr size_t LDS_LIMIT = 160 * 1024 - 512;
+
+// lets KERNEL be launched with up to `bytes` of dynamic LDS (the runtime's default limit is
+// 64 KB): set once per kernel
+template <auto KERNEL>
+void allow_dynamic_lds(int bytes) {
+  static bool set = false;
+  if (set) return;
+  (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            bytes);
+  set = true;
+}
 
 // Cooperative global -> LDS fill with U loads in flight per lane (a plain copy
 // loop exposes one full memory latency per iteration).  `val(i)` produces
@@ -1419,21 +1429,13 @@ k_solve_decoupled(LevDev lv, const double *__restrict__ w, double *__restrict__ 
 // either side gives the own rows exactly -- the same decay the chunk decoupling relies on.
 // No factor tables are read at all (the band is 2 doubles per row); same rows per workgroup
 // as k_solve_decoupled (DEC_CHUNKS * q), so the residual / A'v tail bookkeeping is unchanged.
-typedef double v2d __attribute__((ext_vector_type(2)));
+// The arithmetic of a window -- its rows, the elimination step, the levels, x = d / b, the A'v
+// pair tail and the residual of the own rows -- is written once, in pcr_window.h; the kernels
+// below keep what differs: which inputs they load first, how the right-hand side comes about,
+// what they test or add.
 constexpr int PCR_RMAX = 4 * 66 + 2 * (1 << PCR_LMAX) + 8;        // window rows (q <= 66)
 constexpr int PCR_NR = (PCR_RMAX + IPX_BLOCK - 1) / IPX_BLOCK;    // rows per lane (k_pcr_check)
 constexpr int PCR_TB = 512;                                       // lanes per workgroup of k_solve_pcr
-
-// The matrix is symmetric: only the sub-diagonal a_i = S[i][i-h] is carried (c_i = a_{i+h}
-// is read from the neighbour), with the reciprocal of the diagonal next to it so that a level
-// costs one v_rcp_f64 + one Newton step per row instead of two IEEE divisions:
-//     al = -a_i r_{i-h},  ga = -a_{i+h} r_{i+h}           (r = 1/b)
-//     a_i <- al a_{i-h},  b_i <- b_i + al a_i + ga a_{i+h},  d_i <- d_i + al d_{i-h} + ga d_{i+h}
-// Rows outside the window (or the matrix) are identity rows with a = 0: no bounds branches.
-__device__ __forceinline__ double pcr_rcp(double b) {
-  double r = __builtin_amdgcn_rcp(b);
-  return __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);      // one Newton step: full precision
-}
 
 // Factor-time check in ONE launch: the reduction of the matrix alone (no right-hand side) on
 // the same windows as the solve, all PCR_LMAX levels; a workgroup tests its own rows after
@@ -1445,41 +1447,31 @@ __device__ __forceinline__ double pcr_rcp(double b) {
 // kernel's 78 at m = 1e5 (1540 waves x 7 levels), half of a refactorization.
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_pcr_check(int m, int rows_wg, int nwin, const double *__restrict__ band, int *flags) {
-  constexpr int PAD = 1 << PCR_LMAX;
+  constexpr int PAD = PCR_PAD;
   constexpr int RS = PCR_RMAX + 2 * PAD;
   __shared__ double pa[2][RS], pr[2][RS];
   const int wg = ipx_xcd_item(blockIdx.x, nwin);     // the solve's windows, the solve's placement
   if (wg < 0) return;
-  const int H = 1 << PCR_LMAX;
-  const int R = rows_wg + 2 * H;
-  const int64_t g0 = (int64_t)wg * rows_wg - H;
   const int tid = threadIdx.x;
+  const PcrWindow win(wg, rows_wg, PCR_LMAX, m, tid);
+  const int R = win.R;
   double a[PCR_NR], b[PCR_NR], b0[PCR_NR];
   bool own[PCR_NR];
 #pragma unroll
   for (int k = 0; k < PCR_NR; ++k) {
     const int r = tid + k * IPX_BLOCK;
-    const int64_t g = g0 + r;
-    const bool in = r < R && g >= 0 && g < m;
-    const int64_t gc = min(max(g, (int64_t)0), (int64_t)m - 1);
-    const double bv = band[gc], av = band[(int64_t)m + gc];
-    a[k] = (in && g >= 1 && r >= 1) ? av : 0.0;
-    b[k] = in ? bv : 1.0;
+    win.row_load(band, r, a[k], b[k]);
     b0[k] = b[k];
-    own[k] = in && r >= H && r < H + rows_wg;
+    own[k] = win.own(r);
   }
-  for (int i = tid; i < 2 * PAD; i += IPX_BLOCK) {
-    const int r = i < PAD ? i : R + i;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) { pa[u][r] = 0.0; pr[u][r] = 1.0; }
-  }
+  pcr_pad_identity<IPX_BLOCK, false>(R, tid, pa, pr);
   const double tiny = 1.3877787807814457e-17;                     // 2^-56
   for (int s = 0; s < PCR_LMAX; ++s) {
     const int h = 1 << s, cur = s & 1;
 #pragma unroll
     for (int k = 0; k < PCR_NR; ++k) {
       const int r = tid + k * IPX_BLOCK;
-      if (r < R) { pa[cur][PAD + r] = a[k]; pr[cur][PAD + r] = pcr_rcp(b[k]); }
+      if (r < R) { pa[cur][PAD + r] = a[k]; pr[cur][PAD + r] = ipx_rcp_newton(b[k]); }
     }
     ipx_lds_barrier();
     int bits = 0;
@@ -1488,10 +1480,9 @@ k_pcr_check(int m, int rows_wg, int nwin, const double *__restrict__ band, int *
       const int r = PAD + min(tid + k * IPX_BLOCK, R - 1);
       const double alo = pa[cur][r - h], rlo = pr[cur][r - h];
       const double ahi = pa[cur][r + h], rhi = pr[cur][r + h];
-      const double al = -a[k] * rlo, ga = -ahi * rhi;
-      double bn = __builtin_fma(al, a[k], b[k]);
-      bn = __builtin_fma(ga, ahi, bn);
-      a[k] = al * alo; b[k] = bn;
+      double none = 0.0;
+      pcr_eliminate<false>(a[k], b[k], none, alo, rlo, 0.0, ahi, rhi, 0.0);
+      const double bn = b[k];
       if (own[k]) {
         // a coupling is tested against the diagonal entries of BOTH its rows: a[k] (to row
         // i - 2h) here, and the coupling to row i + 2h -- formed as row i + 2h forms its own
@@ -1517,39 +1508,6 @@ k_pcr_check(int m, int rows_wg, int nwin, const double *__restrict__ band, int *
   }
 }
 
-// The L reduction levels of the solve kernels on one window (k_solve_pcr, k_step1_solve_tail):
-// lane t carries window rows t + k TB in a / b / d; the two LDS buffers alternate by level, their
-// identity padding (PAD rows either side) is the caller's.
-template <int NR, int TB, int RS>
-__device__ __forceinline__ void pcr_levels(int L, int R, int tid, double (&a)[NR], double (&b)[NR],
-                                           double (&d)[NR], double (&pa)[2][RS],
-                                           double (&pr)[2][RS], double (&pd)[2][RS]) {
-  constexpr int PAD = 1 << PCR_LMAX;
-  for (int s = 0; s < L; ++s) {
-    const int h = 1 << s, cur = s & 1;
-    double rc[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int r = tid + k * TB;
-      rc[k] = pcr_rcp(b[k]);
-      if (r < R) { pa[cur][PAD + r] = a[k]; pr[cur][PAD + r] = rc[k]; pd[cur][PAD + r] = d[k]; }
-    }
-    ipx_lds_barrier();
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-      const int r = PAD + min(tid + k * TB, R - 1);
-      const double alo = pa[cur][r - h], rlo = pr[cur][r - h], dlo = pd[cur][r - h];
-      const double ahi = pa[cur][r + h], rhi = pr[cur][r + h], dhi = pd[cur][r + h];
-      const double al = -a[k] * rlo, ga = -ahi * rhi;
-      double bn = __builtin_fma(al, a[k], b[k]);
-      bn = __builtin_fma(ga, ahi, bn);
-      double dn = __builtin_fma(al, dlo, d[k]);
-      dn = __builtin_fma(ga, dhi, dn);
-      a[k] = al * alo; b[k] = bn; d[k] = dn;
-    }
-  }
-}
-
 // TB lanes per workgroup: 512 (PCR_TB) -- measured against 256 and 1024 at n = 1e6 / 4e6: the
 // solve with its tail 10.4 / 28.8 us against 10.8 / 29.9 (256) and 12.6 / 38.6 (1024: one
 // workgroup per CU); the form that builds its own right-hand side (config 5) 7.9 us against
@@ -1561,8 +1519,7 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
             const double *__restrict__ guard, AtvJob atv, RowsJob rows = RowsJob{},
             PostJob post = PostJob{}) {
   constexpr int QA = QV > 0 ? QV : 1;
-  constexpr int PAD = 1 << PCR_LMAX;                 // identity rows either side of the window
-  constexpr int RS = PCR_RMAX + 2 * PAD;
+  constexpr int RS = PCR_RMAX + 2 * PCR_PAD;
   __shared__ double pa[2][RS], pr[2][RS], pd[2][RS];
   __shared__ double sx[PCR_RMAX];
   __shared__ double red_lds[TB / IPX_WAVE];
@@ -1580,11 +1537,10 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
     avn = atv.vown[wg + 1] - av0;
   }
   const double stop = guard ? *guard : 0.0;
-  const int H = 1 << L;
-  const int R = rows_wg + 2 * H;
-  const int64_t own0 = (int64_t)wg * rows_wg;
-  const int64_t g0 = own0 - H;                      // global row of window row 0
   const int tid = threadIdx.x;
+  const PcrWindow win(wg, rows_wg, L, m, tid);
+  const int H = win.H, R = win.R;
+  const int64_t g0 = win.row(0);                       // global row of window row 0
   // ROWS: the entries of the window's rows, the head of the kernel's only dependent chain
   // (entries -> gather of x -> LDS -> row sums), requested before everything else
   extern __shared__ double rows_prod[];              // R rows of (2^logL + 1) doubles (padded)
@@ -1606,14 +1562,9 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
   double a[NR], b[NR], d[NR];
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
-    const int64_t g = g0 + tid + k * TB;
-    const bool in = tid + k * TB < R && g >= 0 && g < m;
-    const int64_t gc = min(max(g, (int64_t)0), (int64_t)m - 1);
-    const double bv = band[gc], av = band[(int64_t)m + gc];
-    a[k] = (in && g >= 1 && tid + k * TB >= 1) ? av : 0.0;     // (row 0 of the window: cut)
-    b[k] = in ? bv : 1.0;
+    const bool in = win.row_load(band, tid + k * TB, a[k], b[k]);
     if constexpr (!ROWS) {
-      const double wv = w[gc];
+      const double wv = w[win.clamped(tid + k * TB)];
       d[k] = in ? wv : 0.0;
     }
   }
@@ -1631,8 +1582,7 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
       const int r = tid + k * TB;
-      const int64_t g = g0 + r;
-      const bool in = r < R && g >= 0 && g < m;
+      const bool in = win.inside(r);
       double sum = 0.0;
       if (in) {
         const double *pr_ = rows_prod + r * (Lr + 1);
@@ -1642,25 +1592,14 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
     }
   }
   // A'v tail: the two ELL entries of every variable and r, requested now so that they arrive
-  // while the reduction runs.  A lane takes PAIRS of consecutive variables (16-byte loads of
-  // the values and of r, 8-byte loads of the columns: half the load instructions -- the tail
-  // is bound by the CU's load issue, 2600 variables x 5 arrays per workgroup); pairs start at
-  // an even variable so every load is naturally aligned (the planes are padded to even length)
+  // while the reduction runs (PcrPairTail: 2600 variables x 5 arrays per workgroup)
   constexpr int QP = (QA + 1) / 2;
-  const int64_t vb = av0 & ~1;                       // first pair (may start one before av0)
-  unsigned ac[QP];                                   // (two 16-bit row offsets)
-  v2d aw0[QP], aw1[QP], ar[QP];
-  if (QV > 0) {
-    const int64_t last = max((int64_t)av0 + avn - 1, vb) & ~(int64_t)1;
-#pragma unroll
-    for (int k = 0; k < QP; ++k) {
-      const int64_t j = min(vb + 2 * (int64_t)(tid + k * TB), last);
-      ac[k] = *reinterpret_cast<const unsigned *>(atv.ell_row + j);
-      aw0[k] = *reinterpret_cast<const v2d *>(atv.ell_val + j);
-      aw1[k] = *reinterpret_cast<const v2d *>(atv.ell_val + atv.ell_n + j);
+  PcrPairTail<QP, TB> tail;
+  v2d ar[QP];
+  if (QV > 0)
+    tail.load(atv.ell_row, atv.ell_val, atv.ell_n, av0, avn, tid, [&](int k, int64_t j) {
       ar[k] = *reinterpret_cast<const v2d *>(atv.r_in + j);
-    }
-  }
+    });
   // POST tail: the operands of this workgroup's items, requested now (the products of the ROWS
   // form are in LDS, their registers free) so that they arrive while the reduction runs
   int pg0 = 0, pgn = 0, pe0 = 0, pen = 0;
@@ -1699,61 +1638,21 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
 #pragma unroll
   for (int k = 0; k < NR; ++k) { a0[k] = a[k]; b0[k] = b[k]; w0[k] = d[k]; }
   IPX_STAMP(2);
-  // identity padding: rows [-PAD, 0) and [R, R + PAD) of both buffers (a = 0, r = 1, d = 0)
-  for (int i = tid; i < 2 * PAD; i += TB) {
-    const int r = i < PAD ? i : R + i;              // storage index = window row + PAD
-#pragma unroll
-    for (int u = 0; u < 2; ++u) { pa[u][r] = 0.0; pr[u][r] = 1.0; pd[u][r] = 0.0; }
-  }
-  // (a of the row just past the window's end is its coupling into the window: cut too)
+  // (a of the row just past the window's end is its coupling into the window: cut by the
+  // identity padding too)
+  pcr_pad_identity<TB, true>(R, tid, pa, pr, pd);
   pcr_levels<NR, TB>(L, R, tid, a, b, d, pa, pr, pd);
   IPX_STAMP(3);
-  // ---- x = d / b; own rows to memory, the window to LDS for the tail / residual
-#pragma unroll
-  for (int k = 0; k < NR; ++k) {
-    const int r = tid + k * TB;
-    if (r < R) {
-      const double xv = d[k] / b[k];
-      sx[r] = xv;
-      const int64_t g = g0 + r;
-      if (r >= H && r < H + rows_wg && g < m) x[g] = xv;
-    }
-  }
+  pcr_solution_to_lds<NR, TB>(win, tid, d, b, sx, x);
   if (!partial && QV == 0 && !POST) return;
   ipx_lds_barrier();
   IPX_STAMP(6);
   if (QV > 0) {
-    // ---- g = r - A'v on this workgroup's variables, v out of LDS (sx)
-    double gacc = 0.0;
-#pragma unroll
-    for (int k = 0; k < QP; ++k) {
-      const int64_t j = vb + 2 * (int64_t)(tid + k * TB);
-      // (an absent entry carries value 0: same sum as the CSR row; a pair that reaches into a
-      // neighbour's variables reads that workgroup's offsets -- in range, result unused)
-      const int c0 = H + (int)(ac[k] & 0xffffu), c1 = H + (int)(ac[k] >> 16);
-      double y0 = -atv.sign * (aw0[k].x * sx[c0] + aw1[k].x * sx[c0 + 1]);
-      y0 += atv.sign * ar[k].x;
-      double y1 = -atv.sign * (aw0[k].y * sx[c1] + aw1[k].y * sx[c1 + 1]);
-      y1 += atv.sign * ar[k].y;
-      const bool in0 = j >= av0 && j < (int64_t)av0 + avn;
-      const bool in1 = j + 1 >= av0 && j + 1 < (int64_t)av0 + avn;
-      if (in0 && in1) {
-        *reinterpret_cast<v2d *>(atv.g_out + j) = (v2d){y0, y1};
-        gacc += y0 * y0;
-        gacc += y1 * y1;
-      } else if (in0) {
-        atv.g_out[j] = y0;
-        gacc += y0 * y0;
-      } else if (in1) {
-        atv.g_out[j + 1] = y1;
-        gacc += y1 * y1;
-      }
-    }
-    const double gtot = ipx_block_reduce<IPX_SUM>(gacc, red_lds);
-    if (tid == 0) {
-      atv.part3[wg] = gtot;
-      atv.part3[nwin + wg] = 0.0;
-    }
+    // ---- g = r - A'v on this workgroup's variables, v out of LDS (sx), r out of registers
+    const double gacc = tail.apply(
+        sx, H, atv.sign, tid, atv.g_out,
+        [&](int k, int64_t, int half) { return half ? ar[k].y : ar[k].x; }, [](int, bool, bool) {});
+    pcr_partial_pair<TB>(gacc, red_lds, atv.part3, wg, nwin, tid);
     if (!partial) return;
   }
   if constexpr (POST) {
@@ -1823,27 +1722,8 @@ k_solve_pcr(int m, int rows_wg, int L, int nwin, const double *__restrict__ band
     }
     if (!partial) return;
   }
-  // ---- residual of the own rows:  w_i - (a_i x_{i-1} + b_i x_i + a_{i+1} x_{i+1})
-  // (a_{i+1} of the row below: the level-0 sub-diagonal of the neighbouring lane, via LDS)
-#pragma unroll
-  for (int k = 0; k < NR; ++k) {
-    const int r = tid + k * TB;
-    if (r < R) pa[0][PAD + r] = a0[k];
-  }
-  ipx_lds_barrier();
-  double acc = 0.0;
-#pragma unroll
-  for (int k = 0; k < NR; ++k) {
-    const int r = tid + k * TB;
-    const int64_t g = g0 + r;
-    if (r >= H && r < H + rows_wg && g < m) {
-      double sum = b0[k] * sx[r];
-      sum += a0[k] * sx[r - 1];
-      sum += pa[0][PAD + r + 1] * sx[r + 1];
-      const double res = w0[k] - sum;
-      acc += res * res;
-    }
-  }
+  // ---- residual of the own rows
+  const double acc = pcr_own_residual<NR, TB>(win, tid, a0, b0, w0, pa[0], sx);
   const double tot = ipx_block_reduce<IPX_SUM>(acc, red_lds);
   if (tid == 0) partial[wg] = tot;
   IPX_STAMP(7);
@@ -1880,26 +1760,15 @@ int launch_solve_pcr_rows(const LevDev &lv, int L, const RowsJob &rows, double *
   const int grid = (lv.P + DEC_CHUNKS - 1) / DEC_CHUNKS;
   if (npartial) *npartial = grid;
   const size_t lds = (size_t)R * ((1 << rows.logL) + 1) * sizeof(double);
-  static bool attr_set = false;
-  if (!attr_set) {
-    // (the kernel's static arrays take 41 KB of the CU's 160: the attribute is the dynamic part)
-    (void)hipFuncSetAttribute((const void *)k_solve_pcr<0, 1, true, PCR_TB>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(LDS_LIMIT - 44 * 1024));
-    attr_set = true;
-  }
+  // (the kernel's static arrays take 41 KB of the CU's 160: the attribute is the dynamic part)
+  constexpr int dyn = (int)(LDS_LIMIT - 44 * 1024);
   if (post) {
-    static bool attr_post = false;
-    if (!attr_post) {
-      (void)hipFuncSetAttribute((const void *)k_solve_pcr<0, 1, true, PCR_TB, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(LDS_LIMIT - 44 * 1024));
-      attr_post = true;
-    }
+    allow_dynamic_lds<k_solve_pcr<0, 1, true, PCR_TB, true>>(dyn);
     hipLaunchKernelGGL((k_solve_pcr<0, 1, true, PCR_TB, true>), dim3(ipx_xcd_grid(grid)),
                        dim3(PCR_TB), lds, st, lv.m, rows_wg, L, grid, lv.band, nullptr, x, partial,
                        guard, AtvJob{}, rows, *post);
   } else {
+    allow_dynamic_lds<k_solve_pcr<0, 1, true, PCR_TB>>(dyn);
     hipLaunchKernelGGL((k_solve_pcr<0, 1, true, PCR_TB>), dim3(ipx_xcd_grid(grid)), dim3(PCR_TB),
                        lds, st, lv.m, rows_wg, L, grid, lv.band, nullptr, x, partial, guard,
                        AtvJob{}, rows);
@@ -1908,18 +1777,21 @@ int launch_solve_pcr_rows(const LevDev &lv, int L, const RowsJob &rows, double *
   return IPX_OK;
 }
 
+// Variables per lane of the A'v tail at PCR_TB lanes, from qv, the count at the 192 lanes the
+// ownership tables are made for: the tail's lanes are the whole 512-thread workgroup, fewer
+// variables each (+1: pairs start at an even variable, possibly one before the workgroup's
+// first).  qv <= 16, the most the tables allow, is a workgroup that owns ~3000 variables -- e.g.
+// a problem of a single 260-row block with 11 columns per row (tests/fuzz_fused_loop.py): 6 per
+// lane; the benchmark's 2600: 6 as well.
+int pcr_tail_per_lane(int qv) { return (qv * (DOWN_T - IPX_WAVE) + 1 + PCR_TB - 1) / PCR_TB; }
+
 int launch_solve_pcr(const LevDev &lv, int L, const double *w, double *x, double *partial,
                      int *npartial, const double *guard, hipStream_t st,
                      const AtvJob *atv = nullptr, int qv = 0) {
   const AtvJob none{};
   if (!atv || qv <= 0)
     return launch_solve_pcr_q<0>(lv, L, w, x, partial, npartial, guard, none, st);
-  // the tail's lanes are the whole 512-thread workgroup (not the 192 the tables count with):
-  // fewer variables each (+1: pairs start at an even variable, possibly one before the
-  // workgroup's first).  qv <= 16, the most the tables allow, is a workgroup that owns ~3000
-  // variables -- e.g. a problem of a single 260-row block with 11 columns per row
-  // (tests/fuzz_fused_loop.py): 6 per lane; the benchmark's 2600: 6 as well
-  const int per = (qv * (DOWN_T - IPX_WAVE) + 1 + PCR_TB - 1) / PCR_TB;
+  const int per = pcr_tail_per_lane(qv);
   if (per <= 2) return launch_solve_pcr_q<2>(lv, L, w, x, partial, npartial, guard, *atv, st);
   if (per <= 4) return launch_solve_pcr_q<4>(lv, L, w, x, partial, npartial, guard, *atv, st);
   if (per <= 6) return launch_solve_pcr_q<6>(lv, L, w, x, partial, npartial, guard, *atv, st);
@@ -1935,11 +1807,17 @@ int launch_solve_pcr(const LevDev &lv, int L, const double *w, double *x, double
 // the row sums of A on the window's rows (one lane per row, entries out of an ELL-transposed
 // copy of A: coalesced) and goes on as k_solve_pcr<QV, 1, false, PCR_TB> does: same grid, same
 // windows, same vown ownership, same arithmetic (1.5 x the products of A, no r_next and no w
-// round trip through memory, one launch less).  Every sum is formed in the order of the launches
-// it replaces: the p'Hp fold by the first 256 lanes as ipx_fold_regs<1, 6> does it in a
-// workgroup of IPX_BLOCK, the row sums left to right, part3 / part4 by k_solve_pcr's lane-to-
-// variable mapping -- the same bits.  g goes to a buffer that is not r_in (a neighbour's window
-// still reads the entries this workgroup owns).
+// round trip through memory, one launch less).  The levels are the shared pcr_levels; the window,
+// the padding, x = d / b, the pair tail and the residual are WRITTEN OUT here, in step with
+// PcrWindow::row_load, pcr_pad_identity, pcr_solution_to_lds, PcrPairTail and pcr_own_residual
+// (pcr_window.h): this kernel's time follows its instruction schedule -- with any one of the five
+// as a call the compiler orders it differently, and every such build measured 0.2 to 0.9 % below
+// this text on the bare loop.  tests/test_gpu_pcr_family_bits.py holds the
+// written-out forms and the helpers to the same bits.  Every sum is
+// formed in the order of the launches it replaces: the p'Hp fold by the first 256 lanes as
+// ipx_fold_regs<1, 6> does it in a workgroup of IPX_BLOCK, the row sums left to right, part3 /
+// part4 by PcrPairTail's lane-to-variable mapping and pcr_own_residual's -- the same bits.  g goes
+// to a buffer that is not r_in (a neighbour's window still reads the entries this workgroup owns).
 // XN as in k_cg_step1_ar: 0 partials of ||x + alpha p||^2 over the own variables (one per
 // workgroup); 1 not formed; 2 the first `ncomp` workgroups fold a slice of the carried sums.
 // PRIME: the projection alone, for the priming (csrc/cg.hip prime_project_tail): no step -- the
@@ -2080,7 +1958,7 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
     if (j < nspan) span[j] = PRIME ? sr[k] : sr[k] + alpha * sh[k];   // :622
   }
   // A' on the own variables (and x, p for the radius test), requested now: they arrive while the
-  // row sums and the reduction run.  Pairs of variables as in k_solve_pcr.
+  // row sums and the reduction run.  Pairs of variables: PcrPairTail::load's loads, in its order.
   const int64_t vb = av0 & ~1;
   unsigned ac[QP];
   v2d aw0[QP], aw1[QP], ax[XN == 0 ? QP : 1], ap[XN == 0 ? QP : 1];
@@ -2124,7 +2002,7 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
     if (tid >= H && tid < H + rows_wg && grow < m) J.v[grow] = xv;
   }
   ipx_lds_barrier();
-  // ---- g = r_next - A'v on this workgroup's variables (k_solve_pcr's tail, r_next out of LDS)
+  // ---- g = r_next - A'v on this workgroup's variables (PcrPairTail::apply, r_next out of LDS)
   double gacc = 0.0, xacc = 0.0;
 #pragma unroll
   for (int k = 0; k < QP; ++k) {
@@ -2169,7 +2047,7 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
       J.part2[nwin + wg] = 0.0;
     }
   }
-  // ---- residual of the own rows (k_solve_pcr's)
+  // ---- residual of the own rows (pcr_own_residual)
   if (tid < R) pa[0][PAD + tid] = a0;
   ipx_lds_barrier();
   double acc = 0.0;
@@ -2219,9 +2097,6 @@ int launch_step1_solve_tail_q(const LevDev &lv, int L, const ipx_fused_proj_job 
                   : launch_step1_solve_tail_qc<QV, false>(lv, L, J, nwin, st);
 }
 
-// variables per lane of the tail at PCR_TB lanes (launch_solve_pcr's count)
-int pcr_tail_per_lane(int qv) { return (qv * (DOWN_T - IPX_WAVE) + 1 + PCR_TB - 1) / PCR_TB; }
-
 
 template <int K>
 size_t decoupled_lds_doubles(int q) {
@@ -2237,12 +2112,7 @@ template <int K, int QV>
 int launch_solve_decoupled_q(const LevDev &lv, const double *w, double *x, const double *rinv,
                              double *partial, int *npartial, const double *guard,
                              const AtvJob &atv, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_solve_decoupled<K, DEC_CHUNKS, QV>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-    attr_set = true;
-  }
+  allow_dynamic_lds<k_solve_decoupled<K, DEC_CHUNKS, QV>>((int)LDS_LIMIT);
   const int grid = (lv.P + DEC_CHUNKS - 1) / DEC_CHUNKS;
   if (npartial) *npartial = grid;
   hipLaunchKernelGGL((k_solve_decoupled<K, DEC_CHUNKS, QV>), dim3(grid), dim3(DOWN_T),
@@ -2273,12 +2143,7 @@ int launch_solve_decoupled(const LevDev &lv, const double *w, double *x, const d
 template <int K>
 int launch_down0(const LevDev &lv, size_t lds, const double *w, double *y, double *gL,
                  double *gR, const double *guard, hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_down0<K, DOWN_CHUNKS>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-    attr_set = true;
-  }
+  allow_dynamic_lds<k_down0<K, DOWN_CHUNKS>>((int)LDS_LIMIT);
   const int grid = (lv.P + DOWN_CHUNKS - 1) / DOWN_CHUNKS;
   hipLaunchKernelGGL((k_down0<K, DOWN_CHUNKS>), dim3(grid), dim3(DOWN_T), lds, st, lv, w, y, gL,
                      gR, guard);
@@ -2290,12 +2155,7 @@ template <int K1, bool STAGED>
 int launch_middle_impl(const LevArgs &a, int nbuf_total, const double *slab, int nslab,
                        const double *gL, const double *gR, double *xs, const double *guard,
                        hipStream_t st) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_middle<K1, STAGED>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-    attr_set = true;
-  }
+  allow_dynamic_lds<k_middle<K1, STAGED>>((int)LDS_LIMIT);
   const size_t lds = ((size_t)nbuf_total + (STAGED ? nslab : 0)) * sizeof(double);
   hipLaunchKernelGGL((k_middle<K1, STAGED>), dim3(1), dim3(MID_T), lds, st, a, nbuf_total, slab,
                      nslab, gL, gR, xs, guard);
@@ -2318,12 +2178,7 @@ struct Launch {
     constexpr int T = factor_chunks_per_wg<K>();
     const size_t lds = factor_lds_doubles<K>(lv.q) * sizeof(double);
     if (lds <= LDS_LIMIT) {
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)k_factor_lds<K, T>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-        attr_set = true;
-      }
+      allow_dynamic_lds<k_factor_lds<K, T>>((int)LDS_LIMIT);
       hipLaunchKernelGGL((k_factor_lds<K, T>), dim3((lv.P + T - 1) / T), dim3(DOWN_T), lds, st,
                          lv.m, lv.c, lv.P, lv.band, lv.Dinv, lv.L, lv.V, lv.W, h->flag);
     } else {
@@ -2966,13 +2821,16 @@ k_band_add(int m, const double *__restrict__ xa, const double *__restrict__ d,
   if (i < m) x[i] = xa[i] + d[i];
 }
 
+// the single-launch decoupled solve at the level's half bandwidth (launch_solve_decoupled
+// refuses the A'v tail beyond half bandwidth 4)
+template <int K = 1>
 int solve_decoupled_k(const LevDev &lv, const double *w, double *x, const double *rinv,
-                      const double *guard, hipStream_t st) {
-  switch (lv.k) {
-#define SD(kk) case kk: return launch_solve_decoupled<kk>(lv, w, x, rinv, nullptr, nullptr, guard, st)
-    SD(1); SD(2); SD(3); SD(4); SD(5); SD(6); SD(7); SD(8);
-#undef SD
-  }
+                      double *partial, int *npartial, const double *guard, hipStream_t st,
+                      const AtvJob *atv = nullptr, int qv = 0) {
+  if (lv.k == K)
+    return launch_solve_decoupled<K>(lv, w, x, rinv, partial, npartial, guard, st, atv, qv);
+  if constexpr (K < KMAX)
+    return solve_decoupled_k<K + 1>(lv, w, x, rinv, partial, npartial, guard, st, atv, qv);
   return IPX_EINVAL;
 }
 
@@ -2991,13 +2849,13 @@ int iter_solve(Banded *h, const double *w, double *x, double *partial, int *npar
   const int m = lv.m;
   double *xa = h->iter_buf, *xb = xa + m, *r = xb + m, *d = r + m;
   const dim3 grid((m + IPX_BLOCK - 1) / IPX_BLOCK), block(IPX_BLOCK);
-  int rc = solve_decoupled_k(lv, w, xa, h->rinv, guard, st);
+  int rc = solve_decoupled_k(lv, w, xa, h->rinv, nullptr, nullptr, guard, st);
   if (rc != IPX_OK) return rc;
   hipLaunchKernelGGL(k_band_update_resid, grid, block, 0, st, m, lv.k, lv.band, w, xa,
                      (const double *)nullptr, (double *)nullptr, r, guard);
   IPX_CHECK_LAUNCH();
   for (int it = 1; it <= h->iter_N; ++it) {
-    rc = solve_decoupled_k(lv, r, d, h->rinv, guard, st);
+    rc = solve_decoupled_k(lv, r, d, h->rinv, nullptr, nullptr, guard, st);
     if (rc != IPX_OK) return rc;
     if (it < h->iter_N) {
       hipLaunchKernelGGL(k_band_update_resid, grid, block, 0, st, m, lv.k, lv.band, w, xa, d, xb, r,
@@ -3030,15 +2888,9 @@ int fast_solve(Banded *h, const double *w, double *x, double *partial, int *npar
     if (rc != IPX_OK) return rc;
     return fast_solve(h, w, x, partial, npartial, guard, st);     // (by the verdict just read)
   }
-  if (h->decoupled && w != x) {
-    const LevDev lv = to_dev(h->lev[0], nullptr);
-    switch (lv.k) {
-#define SD(kk) case kk: return launch_solve_decoupled<kk>(lv, w, x, h->rinv, partial, npartial, guard, st)
-      SD(1); SD(2); SD(3); SD(4); SD(5); SD(6); SD(7); SD(8);
-#undef SD
-    }
-    return IPX_EINVAL;
-  }
+  if (h->decoupled && w != x)
+    return solve_decoupled_k(to_dev(h->lev[0], nullptr), w, x, h->rinv, partial, npartial, guard,
+                             st);
   if (h->iter_N > 0 && !h->decoupled) {
     // (x may alias w as the contract of ipx_banded_solve says: the correction steps read w
     // and write scratch, x is only written by the last launch; the residual partials read w
@@ -3115,14 +2967,8 @@ int ipx_banded_solve_resid_atv_launch(void *handle, const double *w, double *x, 
     if (rc != IPX_OK) return rc;
     if (!ipx_banded_decoupled_geometry(handle, geo)) return IPX_EINVAL;
   }
-  const LevDev lv = to_dev(h->lev[0], nullptr);
-  switch (lv.k) {
-    case 1: return launch_solve_decoupled<1>(lv, w, x, h->rinv, partial, npartial, guard, st, &job, qv);
-    case 2: return launch_solve_decoupled<2>(lv, w, x, h->rinv, partial, npartial, guard, st, &job, qv);
-    case 3: return launch_solve_decoupled<3>(lv, w, x, h->rinv, partial, npartial, guard, st, &job, qv);
-    case 4: return launch_solve_decoupled<4>(lv, w, x, h->rinv, partial, npartial, guard, st, &job, qv);
-  }
-  return IPX_EINVAL;
+  return solve_decoupled_k(to_dev(h->lev[0], nullptr), w, x, h->rinv, partial, npartial, guard, st,
+                           &job, qv);
 }
 
 // The projection half of a CG iteration in one launch (k_step1_solve_tail): only on the cyclic-

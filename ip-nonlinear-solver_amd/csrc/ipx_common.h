@@ -133,6 +133,14 @@ __device__ __forceinline__ double ipx_wave_min(double v) {
   return v;
 }
 
+// 1 / b to full precision from v_rcp_f64 and one Newton step: the cyclic reductions (banded.hip
+// through pcr_window.h, resident.hip) divide by every reduced diagonal entry once per level, and
+// this costs half of two IEEE divisions.  One definition: the kernels must agree bit for bit.
+__device__ __forceinline__ double ipx_rcp_newton(double b) {
+  double r = __builtin_amdgcn_rcp(b);
+  return __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
+}
+
 // Workgroup barrier for exchanges that go through LDS only: waits for this
 // wave's LDS traffic, NOT for its outstanding global loads/stores
 // (__syncthreads() also drains vmcnt -- ~2 us when stores are in flight).

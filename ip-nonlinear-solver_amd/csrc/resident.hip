@@ -151,10 +151,6 @@ __device__ __forceinline__ int res_opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
 }
-__device__ __forceinline__ double res_rcp(double b) {        // (csrc/banded.hip pcr_rcp)
-  double r = __builtin_amdgcn_rcp(b);
-  return __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
-}
 // One granule = the two tagged words of a double, written by ONE 16-byte write-through store
 // (8-byte sc1 stores are one fabric write each and cost 2.7x per byte: MI355X_MICROARCH.md,
 // stores table; every 8-byte half validates itself, so tearing between the halves is harmless).
@@ -660,7 +656,7 @@ k_cg_resident(ResJob J) {
 #pragma unroll
       for (int q = 0; q < RNR; ++q) {
         const int r = tid + q * RB;
-        const double rc = res_rcp(b[q]);
+        const double rc = ipx_rcp_newton(b[q]);
         if (r < R) { pa[H + r] = a[q]; pr_[H + r] = rc; pd[H + r] = d[q]; }
       }
       ipx_lds_barrier();

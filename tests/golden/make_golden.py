@@ -46,6 +46,9 @@ Outputs (numbers only -- no reference source travels; an .npz over 1 MiB is writ
                     subproblem is assembled from: x, s, the multipliers of the nonlinear
                     rows, the slack block of the Hessian, c_t, lb_t, the radius) and what it
                     returned (x, niter, stop_cond, hits_boundary, the first 20 iterates)
+  pcr_family_bits.npz  (``--pcr-family``: ON THE GPU, without the reference) what THIS project's
+                    cyclic-reduction kernels compute on the cases of tests/pcr_family_cases.py,
+                    to the bit; re-recorded only by a change that reorders a sum on purpose
 """
 import json
 import os
@@ -58,6 +61,22 @@ import scipy.sparse as sps
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.dont_write_bytecode = True
+
+
+def pcr_family():
+    """This project's own outputs (needs the GPU and the built library, not the reference)."""
+    for p in (os.path.join(ROOT, "ip-nonlinear-solver_amd"), os.path.join(ROOT, "tests")):
+        sys.path.insert(0, p)
+    import pcr_family_cases
+    out, failed = pcr_family_cases.record()
+    assert not failed, failed
+    np.savez_compressed(os.path.join(HERE, "pcr_family_bits.npz"), **out)
+
+
+if "--pcr-family" in sys.argv:
+    pcr_family()
+    sys.exit(0)
+
 sys.path.insert(0, "/root/reference")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 

@@ -273,18 +273,9 @@ def test_public_call_with_the_priming_projection(monkeypatch):
     assert torch.equal(out[(fused, 0)][0], out[(fused, 1)][0])
 
 
-def test_box_schur_solve_on_nine_windows():
-    """The Schur solve of the barrier-shaped problem (k_solve_pcr forming its own right-hand
-    side, with the per-item tail) at 9 windows, through the public solver, against the host
-    oracle's projected CG: tests/fuzz_box_schur.py's problem and its tolerance (the same
-    iteration count and exit, x to 1e-9)."""
-    import os
-    import ipsolver.device as dv
-    import ipsolver.projector as projector
-    import ipsolver.cg_fused as cg_fused
-    from ipsolver import _hip
-    import oracle
-    os.environ.pop("IPX_DEBUG_FORMS", None)
+def box_schur_nine_windows():
+    """tests/fuzz_box_schur.py's barrier-shaped problem at 2340 general rows (nine windows):
+    (A, H, c, b, lb, keyword arguments of projected_cg)."""
     rng = np.random.default_rng(2340)
     rl, shift, m = 15, 8, 2340
     n = (m - 1) * shift + rl
@@ -305,7 +296,23 @@ def test_box_schur_solve_on_nine_windows():
     c = rng.standard_normal(N)
     b = np.zeros(M)
     lb = np.concatenate((np.full(n, -np.inf), np.full(N - n, -0.995)))
-    kw = dict(trust_radius=np.inf, tol=1e-10, max_iter=40)
+    return A, Hz, c, b, lb, dict(trust_radius=np.inf, tol=1e-10, max_iter=40)
+
+
+def test_box_schur_solve_on_nine_windows():
+    """The Schur solve of the barrier-shaped problem (k_solve_pcr forming its own right-hand
+    side, with the per-item tail) at 9 windows, through the public solver, against the host
+    oracle's projected CG: tests/fuzz_box_schur.py's problem and its tolerance (the same
+    iteration count and exit, x to 1e-9)."""
+    import os
+    import ipsolver.device as dv
+    import ipsolver.projector as projector
+    import ipsolver.cg_fused as cg_fused
+    from ipsolver import _hip
+    import oracle
+    os.environ.pop("IPX_DEBUG_FORMS", None)
+    A, Hz, c, b, lb, kw = box_schur_nine_windows()
+    N = A.shape[1]
     Ad = dv.DeviceCSR.from_scipy(A)
     Z, _, Y = projector.projections(Ad)
     solver = Z.projector.solver
