@@ -190,6 +190,30 @@ int ipx_aat_dense(int64_t m, const int32_t *rowptr, const int32_t *colidx, const
  * work: M + 1 doubles; work[M] <- min pivot / original diagonal (~1/cond(G)). */
 int ipx_chol_factor(int64_t M, double *G, int *flag, double *work, void *stream);
 int ipx_chol_inverse(int64_t M, double *G, double *X, void *stream);
+/* The triangular half of ipx_chol_inverse alone: the lower triangle of G (lower triangular L,
+ * the strict upper triangle of its diagonal tiles zero) <- L^-1 in place; the upper triangle
+ * outside the diagonal tiles is used as scratch. */
+int ipx_trtri_lower(int64_t M, double *G, void *stream);
+
+/* ---- blocked Householder QR of A' for a dense row-major A, m <= n (csrc/denseqr.hip; the
+ * reference's dense factorization, projections.py:175-233, unpivoted).  M = ipx_dense_padded(m),
+ * N = ipx_qr_padded_cols(n).  ipx_qr_factor: W (M x N) <- the reflectors (row j = v_j with its
+ * unit entry), L (M x M) <- R' (lower triangular, identity on the padding), T (M / 64 tiles of
+ * 64 x 64) <- the compact WY factors, tau (M), info[0] <- min_j |R_jj| / ||row j of A||,
+ * info[1 .. M] <- the squared row norms of A.  ipx_qr_form_q: QT (M x N) <- Q' (row r = column r
+ * of Q).  ws: ipx_qr_ws_doubles(m, n) doubles for both.  Plain launches only, every sum in a
+ * fixed order. */
+int64_t ipx_qr_padded_cols(int64_t n);
+int64_t ipx_qr_ws_doubles(int64_t m, int64_t n);
+int ipx_qr_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W, double *L,
+                  double *T, double *tau, double *info, double *ws, void *stream);
+int ipx_qr_form_q(int64_t m, int64_t n, const double *W, const double *T, double *QT, double *ws,
+                  void *stream);
+/* Linv (M x M) <- L^-1 = R^-T, strict upper triangle exactly zero; L is kept. */
+int ipx_qr_tri_inverse(int64_t M, const double *L, double *Linv, void *stream);
+/* y (n) = B' x for a row-major B (m x n, leading dimension ldb), summed in a fixed order. */
+int ipx_dense_gemvt(int64_t m, int64_t n, const double *B, int64_t ldb, const double *x, double *y,
+                    void *stream);
 
 /* ---- dense constraint Jacobians with inequality rows (csrc/densejac.hip; device-callback
  * mode's dense canonical form, _canonical_constraint.py:240-280, :363-438, and the barrier's

@@ -468,6 +468,11 @@ def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, 
         raise NotImplementedError("sparse_direct=%r: the row-sharded backend builds its own "
                                   "(A A')^-1 solvers; the option is available on one GPU only"
                                   % (direct,))
+    dense_fact = solver_options.current().dense_factorization
+    if dense_fact != "normal-equations" and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("dense_factorization=%r: the row-sharded backend builds its own "
+                                  "(A A')^-1 solvers; the option is available on one GPU only"
+                                  % (dense_fact,))
     if _qn.is_strategy(hess) and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "

@@ -12,7 +12,10 @@ benchmark problems.
   * sparse A whose ``AA'`` is banded (after a bandwidth-reducing row order found
     once per sparsity pattern on the host -- symbolic work only): partitioned
     banded LDL' kernels (csrc/banded.hip);
-  * dense A: Gram matrix + dense Cholesky kernels (csrc/dense.hip).
+  * dense A: Gram matrix + dense Cholesky kernels (csrc/dense.hip); under the option
+    ``dense_factorization = "householder-qr"`` the reference's own dense method instead, a
+    Householder QR of ``A'`` on the device (``DenseQRProjector``, dense_qr.py) -- a sparse A
+    ignores the option.
 All numeric work of the full-rank path runs on the GPU.  A numerically rank-deficient
 Jacobian (a pivot of the device factorization lost against its diagonal) takes the
 reference's own exit: a warning and the SVD projections (projections.py:101-108,
@@ -32,6 +35,7 @@ from . import device as dv
 from . import solver_options
 from .device import DVec, DeviceCSR, _p, stream_ptr, ctx
 from .dense import DenseNormalSolver, DeviceDense
+from .dense_qr import DenseQRProjector
 from .device_mode import RowSelection
 # The solvers, their selection and its options live in modules of their own, layered
 #   solver_options < banded < blocktri, blockwide, iterative, nested < band_solver < bordered
@@ -42,7 +46,9 @@ from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link
                              check_wide_band, check_border_columns, check_link_rows,
                              ITERATIVE_PRECONDS, iterative_precond, iterative_precond_choice,
                              check_iterative_precond, SPARSE_DIRECT, sparse_direct,
-                             sparse_direct_choice, check_sparse_direct)
+                             sparse_direct_choice, check_sparse_direct,
+                             DENSE_FACTORIZATIONS, dense_factorization,
+                             dense_factorization_choice, check_dense_factorization)
 from .banded import (BandedNormalSolver, BandedNotDecoupled, HANDLE_STATS, _Symbolic,  # noqa: F401
                      _SYMBOLIC_ATTR, _symbolic_for, half_bandwidth_of_aat)
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: F401
@@ -427,6 +433,11 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
             row_perm = _banded_row_order(A)
             if row_perm is not None:
                 A = _rows_in_order(A, row_perm)
+        if isinstance(A, DeviceDense) and m > 0 \
+                and solver_options.current().dense_factorization == "householder-qr":
+            # (LinAlgError when min |R_jj| / ||a_j|| < 2^-43: the exits below, as for a lost
+            # pivot of the Cholesky factorization)
+            return DenseQRProjector(A, orth_tol, max_refin).operators()
         solver = None if m == 0 else (normal_solver_for(A) if deferred is None
                                       else normal_solver_for(A, deferred))
         inner = getattr(solver, "inner", solver)           # (box-Schur: its banded Schur solve)

@@ -19,6 +19,12 @@ default, so the keys of every setting that existed before it are what they were.
 and (without the option) the dense Cholesky or the preconditioned CG would, is factored by the
 nested-dissection multifrontal Cholesky (nested.py).  Held and keyed like ``iterative_precond``.
 
+``dense_factorization``: "normal-equations" (default): a dense Jacobian is factored as Gram +
+Cholesky (dense.py); "householder-qr": by a blocked Householder QR of ``A'`` on the device
+(dense_qr.py), whose operators lose ``cond(A) eps`` instead of ``cond(A)^2 eps``.  It acts on
+dense device matrices only -- a sparse Jacobian ignores it.  Held and keyed like
+``iterative_precond``.
+
 Scoped: ``with scoped(wide_band="block-tridiagonal", link_rows=4): ...`` holds any subset for the
 duration of the block.  ``current().key()`` is part of the key of every cached factorization: a
 new option is a new name here (``NAMES``, ``check``, ``key``) and nowhere else.
@@ -33,20 +39,25 @@ from . import _hip
 WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide")
 ITERATIVE_PRECONDS = ("block", "compact", "two-level")
 SPARSE_DIRECT = ("off", "nested-dissection")
-NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond", "sparse_direct")
+DENSE_FACTORIZATIONS = ("normal-equations", "householder-qr")
+NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond", "sparse_direct",
+         "dense_factorization")
 # the options held beside the tuple: name -> allowed values, the first the default
-_BESIDE = {"iterative_precond": ITERATIVE_PRECONDS, "sparse_direct": SPARSE_DIRECT}
+_BESIDE = {"iterative_precond": ITERATIVE_PRECONDS, "sparse_direct": SPARSE_DIRECT,
+           "dense_factorization": DENSE_FACTORIZATIONS}
 
 
 class Options(collections.namedtuple("Options", "wide_band border_columns link_rows")):
     iterative_precond = ITERATIVE_PRECONDS[0]      # (attributes beside the tuple's fields)
     sparse_direct = SPARSE_DIRECT[0]
+    dense_factorization = DENSE_FACTORIZATIONS[0]
 
     def __new__(cls, wide_band, border_columns, link_rows, iterative_precond="block",
-                sparse_direct="off"):
+                sparse_direct="off", dense_factorization="normal-equations"):
         self = super().__new__(cls, wide_band, border_columns, link_rows)
         self.iterative_precond = iterative_precond
         self.sparse_direct = sparse_direct
+        self.dense_factorization = dense_factorization
         return self
 
     def _replace(self, **changes):
@@ -61,6 +72,8 @@ class Options(collections.namedtuple("Options", "wide_band border_columns link_r
         extra = () if self.iterative_precond == ITERATIVE_PRECONDS[0] else (self.iterative_precond,)
         if self.sparse_direct != SPARSE_DIRECT[0]:
             extra += (self.sparse_direct,)
+        if self.dense_factorization != DENSE_FACTORIZATIONS[0]:
+            extra += (self.dense_factorization,)
         return tuple(self) + extra
 
 
@@ -108,8 +121,9 @@ def pop_from(options):
     that is not given: the value in force), as the keywords of ``scoped``."""
     held = {name: check(name, options.pop(name, getattr(current(), name)))
             for name in NAMES[:4]}
-    # (``sparse_direct`` only when it is given: without it ``scoped`` leaves the value in force
-    # as it is, and the record of a call that does not use it reads as before the option)
+    # (``sparse_direct`` and ``dense_factorization`` only when given: without it ``scoped``
+    # leaves the value in force as it is, and the record of a call that does not use it reads
+    # as before the option)
     for name in NAMES[4:]:
         if name in options:
             held[name] = check(name, options.pop(name))
@@ -136,3 +150,5 @@ link_rows, link_rows_limit, check_link_rows = _wrappers("link_rows")
 iterative_precond, iterative_precond_choice, check_iterative_precond = \
     _wrappers("iterative_precond")
 sparse_direct, sparse_direct_choice, check_sparse_direct = _wrappers("sparse_direct")
+dense_factorization, dense_factorization_choice, check_dense_factorization = \
+    _wrappers("dense_factorization")
