@@ -209,11 +209,38 @@ int ipx_qr_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W,
                   double *T, double *tau, double *info, double *ws, void *stream);
 int ipx_qr_form_q(int64_t m, int64_t n, const double *W, const double *T, double *QT, double *ws,
                   void *stream);
+/* T (M / 64 tiles) <- the compact WY factors of reflectors W (M x N, ipx_qr_factor's form) and
+ * tau (M) that another factorization made (ipx_qrp_reflectors); ws as for ipx_qr_factor. */
+int ipx_qr_wy(int64_t m, int64_t n, const double *W, const double *tau, double *T, double *ws,
+              void *stream);
 /* Linv (M x M) <- L^-1 = R^-T, strict upper triangle exactly zero; L is kept. */
 int ipx_qr_tri_inverse(int64_t M, const double *L, double *Linv, void *stream);
 /* y (n) = B' x for a row-major B (m x n, leading dimension ldb), summed in a fixed order. */
 int ipx_dense_gemvt(int64_t m, int64_t n, const double *B, int64_t ldb, const double *x, double *y,
                     void *stream);
+
+/* ---- column-pivoted Householder QR of A' for a dense row-major A, m <= n (csrc/denseqrp.hip):
+ * A' P = Q [R11 R12], the rank r = the number of leading j with |R_jj| > 2^-43 |R_00|.  No row
+ * of W (M x N) is moved: iw (ipx_qrp_info_ints(m) ints) = perm (M; perm[j] = the row that is
+ * pivot j, a permutation of 0 .. m - 1 on return) | pos (M) | done, rank; dw
+ * (ipx_qrp_info_doubles(m) doubles) = tau (M) | diag R (M) | the reflectors' scale factors (M) |
+ * the pivot norms of the steps taken, the rejected one included.  ipx_qrp_factor: 2 m + 3 plain
+ * launches enqueued at once, every sum in a fixed order; ws: ipx_qrp_ws_doubles(m, n) doubles.
+ * ipx_qrp_reflectors: Vp (Mr x N, Mr = ipx_dense_padded(r)), taup (Mr) <- the first r reflectors
+ * in pivot order, as ipx_qr_wy / ipx_qr_form_q take them.  ipx_qrp_write_t: T (r x m, leading
+ * dimension ldt) <- [R11 R12], exactly zero below the diagonal.  ipx_qrp_fold_columns:
+ * out[row][perm[c]] <- in[row][c], c < m. */
+int64_t ipx_qrp_ws_doubles(int64_t m, int64_t n);
+int64_t ipx_qrp_info_doubles(int64_t m);
+int64_t ipx_qrp_info_ints(int64_t m);
+int ipx_qrp_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W, double *dw,
+                   int32_t *iw, double *ws, void *stream);
+int ipx_qrp_reflectors(int64_t m, int64_t n, int64_t r, const double *W, const double *dw,
+                       const int32_t *iw, double *Vp, double *taup, void *stream);
+int ipx_qrp_write_t(int64_t m, int64_t n, int64_t r, const double *W, const double *dw,
+                    const int32_t *iw, double *T, int64_t ldt, void *stream);
+int ipx_qrp_fold_columns(int64_t rows, int64_t m, int64_t ld, const double *in, const int32_t *perm,
+                         double *out, void *stream);
 
 /* ---- dense constraint Jacobians with inequality rows (csrc/densejac.hip; device-callback
  * mode's dense canonical form, _canonical_constraint.py:240-280, :363-438, and the barrier's

@@ -372,6 +372,20 @@ int qr_xv(const double *X0, int64_t ldx, const double *V0, int64_t ldv, int K, i
   return IPX_OK;
 }
 
+// The compact WY factor of the panel at row / column j0 of the reflectors W (rows in the clean
+// unit-trapezoidal form): wk[0 .. tiles) <- X V' for the `tiles` row tiles from the panel down
+// (tile 0 is S = V V'), Tp <- T from tau and S.  Three launches.
+int qr_wy_panel(const double *W, int N, int j0, int tiles, const double *tau, double *Tp, double *ws,
+                const QrWs &o, hipStream_t st) {
+  const double *V0 = W + (int64_t)j0 * N + j0;
+  const int rc = qr_xv(V0, N, V0, N, N - j0, tiles, ws, o, st);
+  if (rc != IPX_OK) return rc;
+  hipLaunchKernelGGL(k_qr_tform, dim3(1), dim3(IPX_WAVE), 0, st, (const double *)(ws + o.wk),
+                     (const double *)(tau + j0), Tp);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -428,11 +442,8 @@ int ipx_qr_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W,
     // S = V V' (tile 0) and X V' for the rows behind the panel in one split-K launch
     const int tiles = nt - p, K = N - j0;
     const double *V0 = W + (int64_t)j0 * N + j0;
-    int rc = qr_xv(V0, N, V0, N, K, tiles, ws, o, st);
+    int rc = qr_wy_panel(W, N, j0, tiles, tau, T + (int64_t)p * QTILE, ws, o, st);
     if (rc != IPX_OK) return rc;
-    hipLaunchKernelGGL(k_qr_tform, dim3(1), dim3(IPX_WAVE), 0, st, (const double *)(ws + o.wk),
-                       (const double *)(tau + j0), T + (int64_t)p * QTILE);
-    IPX_CHECK_LAUNCH();
     if (tiles > 1) {
       hipLaunchKernelGGL(k_qr_wt<0>, dim3(tiles - 1), dim3(IPX_BLOCK), 0, st,
                          (const double *)(ws + o.wk + QTILE),
@@ -447,6 +458,22 @@ int ipx_qr_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W,
   hipLaunchKernelGGL(k_qr_ratio, dim3(1), dim3(IPX_BLOCK), 0, st, (int)m, M, (const double *)L,
                      (const double *)(info + 1), info);
   IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+// T (M / 64 tiles) <- the compact WY factors of reflectors that were not made by ipx_qr_factor
+// (the pivoted factorization of csrc/denseqrp.hip): W (M x N) in ipx_qr_factor's form, tau (M).
+// 3 M / 64 launches.
+int ipx_qr_wy(int64_t m, int64_t n, const double *W, const double *tau, double *T, double *ws,
+              void *stream) {
+  if (m < 1 || n < m || !W || !tau || !T || !ws) return IPX_EINVAL;
+  const int M = (int)ipx_dense_padded(m), N = (int)ipx_qr_padded_cols(n);
+  const QrWs o(M, N);
+  for (int p = 0; p < M / QB; ++p) {
+    const int rc = qr_wy_panel(W, N, p * QB, 1, tau, T + (int64_t)p * QTILE, ws, o,
+                               (hipStream_t)stream);
+    if (rc != IPX_OK) return rc;
+  }
   return IPX_OK;
 }
 

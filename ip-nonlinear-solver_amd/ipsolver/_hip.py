@@ -46,7 +46,12 @@ _SIGNATURES = {
     "ipx_trtri_lower": [_I64, _P, _P],
     "ipx_qr_factor": [_I64, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P],
     "ipx_qr_form_q": [_I64, _I64, _P, _P, _P, _P, _P],
+    "ipx_qr_wy": [_I64, _I64, _P, _P, _P, _P, _P],
     "ipx_qr_tri_inverse": [_I64, _P, _P, _P],
+    "ipx_qrp_factor": [_I64, _I64, _P, _I64, _P, _P, _P, _P, _P],
+    "ipx_qrp_reflectors": [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P],
+    "ipx_qrp_write_t": [_I64, _I64, _I64, _P, _P, _P, _P, _I64, _P],
+    "ipx_qrp_fold_columns": [_I64, _I64, _I64, _P, _P, _P, _P],
     "ipx_dense_gemvt": [_I64, _I64, _P, _I64, _P, _P, _P],
     "ipx_dense_gather_rows": [_I64, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _P],
     "ipx_csr_rows_to_dense": [_I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
@@ -188,9 +193,13 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_fd_perturb_host": None, "ipx_fd_assemble_host": None,
              "ipx_fd_assemble_sym_host": None, "ipx_blocktri_ws_doubles": _I64,
              "ipx_blockwide_ws_doubles": _I64, "ipx_nd_symbolic": _I64,
-             "ipx_qr_padded_cols": _I64, "ipx_qr_ws_doubles": _I64}
+             "ipx_qr_padded_cols": _I64, "ipx_qr_ws_doubles": _I64,
+             "ipx_qrp_ws_doubles": _I64, "ipx_qrp_info_doubles": _I64,
+             "ipx_qrp_info_ints": _I64}
 _EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
                    "ipx_qr_padded_cols": [_I64], "ipx_qr_ws_doubles": [_I64, _I64],
+                   "ipx_qrp_ws_doubles": [_I64, _I64], "ipx_qrp_info_doubles": [_I64],
+                   "ipx_qrp_info_ints": [_I64],
                    "ipx_nd_symbolic": [_I64, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64],
                    "ipx_blockwide_ws_doubles": [_I64, _I32],
                    "ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],

@@ -15,7 +15,9 @@ Two deviations from the reference, both in how a rank-deficient matrix is recogn
     convention (``IPX_PIVOT_RTOL``) applied to ``R`` instead of to ``R'R`` -- where the
     reference's is absolute (``||R[-1, :]||_inf < tol``).
 A matrix that fails the test leaves by ``np.linalg.LinAlgError``; ``projector._projections``
-then warns and takes the SVD exit exactly as for the Cholesky path.
+then warns and takes the SVD exit exactly as for the Cholesky path -- or, under the option
+``rank_deficient = "pivoted-qr"``, the device exit of dense_cod.py (``DenseCODProjector``), whose
+QR IS column-pivoted and reveals the rank.
 
 The fused CG loop (cg_fused) does not take this projector (``cg_fused.supports`` is False for
 anything but a ``NormalEquationProjector``): the CG runs the generic loop, ``qp.projected_cg``.

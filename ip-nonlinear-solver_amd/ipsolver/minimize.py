@@ -473,6 +473,11 @@ def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, 
         raise NotImplementedError("dense_factorization=%r: the row-sharded backend builds its own "
                                   "(A A')^-1 solvers; the option is available on one GPU only"
                                   % (dense_fact,))
+    rank_def = solver_options.current().rank_deficient
+    if rank_def != "host-svd" and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("rank_deficient=%r: the row-sharded backend builds its own "
+                                  "(A A')^-1 solvers; the option is available on one GPU only"
+                                  % (rank_def,))
     if _qn.is_strategy(hess) and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "

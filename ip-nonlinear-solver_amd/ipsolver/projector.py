@@ -21,7 +21,9 @@ Jacobian (a pivot of the device factorization lost against its diagonal) takes t
 reference's own exit: a warning and the SVD projections (projections.py:101-108,
 181-187,236-287) -- the thin SVD of the (small, dense) matrix is LAPACK on the host as in
 the reference, its factors are uploaded once and every operator application is device
-matvecs (``SVDProjector``).
+matvecs (``SVDProjector``).  Under the option ``rank_deficient = "pivoted-qr"`` a dense device
+Jacobian with ``1 <= m <= n`` stays on the device instead: a column-pivoted QR and a complete
+orthogonal decomposition (``DenseCODProjector``, dense_cod.py).
 """
 from warnings import warn
 
@@ -36,6 +38,7 @@ from . import solver_options
 from .device import DVec, DeviceCSR, _p, stream_ptr, ctx
 from .dense import DenseNormalSolver, DeviceDense
 from .dense_qr import DenseQRProjector
+from .dense_cod import DenseCODProjector
 from .device_mode import RowSelection
 # The solvers, their selection and its options live in modules of their own, layered
 #   solver_options < banded < blocktri, blockwide, iterative, nested < band_solver < bordered
@@ -48,7 +51,9 @@ from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link
                              check_iterative_precond, SPARSE_DIRECT, sparse_direct,
                              sparse_direct_choice, check_sparse_direct,
                              DENSE_FACTORIZATIONS, dense_factorization,
-                             dense_factorization_choice, check_dense_factorization)
+                             dense_factorization_choice, check_dense_factorization,
+                             RANK_DEFICIENT, rank_deficient, rank_deficient_choice,
+                             check_rank_deficient)
 from .banded import (BandedNormalSolver, BandedNotDecoupled, HANDLE_STATS, _Symbolic,  # noqa: F401
                      _SYMBOLIC_ATTR, _symbolic_for, half_bandwidth_of_aat)
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: F401
@@ -448,6 +453,13 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
                  "the dense SVD fallback: keeping the factorization under iterative refinement.")
     except np.linalg.LinAlgError:
         # the reference's exits: projections.py:101-108 (sparse), :181-187 (dense)
+        if solver_options.current().rank_deficient == "pivoted-qr" \
+                and isinstance(A_caller, DeviceDense) and 1 <= m <= n:
+            # (whichever dense factorization raised: a lost Cholesky pivot, ``ill_conditioned``,
+            # the Householder pivot ratio)
+            warn("Singular Jacobian matrix. Using a pivoted QR decomposition on the device to "
+                 "perform the factorizations.")
+            return DenseCODProjector(A_caller, orth_tol, max_refin).operators()
         warn("Singular Jacobian matrix. Using dense SVD decomposition to perform the "
              "factorizations." if sparse else
              "Singular Jacobian matrix. Using SVD decomposition to perform the "

@@ -25,6 +25,12 @@ Cholesky (dense.py); "householder-qr": by a blocked Householder QR of ``A'`` on 
 dense device matrices only -- a sparse Jacobian ignores it.  Held and keyed like
 ``iterative_precond``.
 
+``rank_deficient``: "host-svd" (default): a Jacobian that a factorization finds numerically rank
+deficient takes the reference's exit, LAPACK's SVD on the host (``SVDProjector``); "pivoted-qr":
+a dense device Jacobian with ``1 <= m <= n`` is factored by a column-pivoted QR on the device
+instead (``DenseCODProjector``, dense_cod.py) -- sparse Jacobians, ``m > n`` and
+``method="SVDFactorization"`` keep the host exit.  Held and keyed like ``iterative_precond``.
+
 Scoped: ``with scoped(wide_band="block-tridiagonal", link_rows=4): ...`` holds any subset for the
 duration of the block.  ``current().key()`` is part of the key of every cached factorization: a
 new option is a new name here (``NAMES``, ``check``, ``key``) and nowhere else.
@@ -40,24 +46,28 @@ WIDE_BAND_POLICIES = ("iterative", "block-tridiagonal", "block-tridiagonal-wide"
 ITERATIVE_PRECONDS = ("block", "compact", "two-level")
 SPARSE_DIRECT = ("off", "nested-dissection")
 DENSE_FACTORIZATIONS = ("normal-equations", "householder-qr")
+RANK_DEFICIENT = ("host-svd", "pivoted-qr")
 NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond", "sparse_direct",
-         "dense_factorization")
+         "dense_factorization", "rank_deficient")
 # the options held beside the tuple: name -> allowed values, the first the default
 _BESIDE = {"iterative_precond": ITERATIVE_PRECONDS, "sparse_direct": SPARSE_DIRECT,
-           "dense_factorization": DENSE_FACTORIZATIONS}
+           "dense_factorization": DENSE_FACTORIZATIONS, "rank_deficient": RANK_DEFICIENT}
 
 
 class Options(collections.namedtuple("Options", "wide_band border_columns link_rows")):
     iterative_precond = ITERATIVE_PRECONDS[0]      # (attributes beside the tuple's fields)
     sparse_direct = SPARSE_DIRECT[0]
     dense_factorization = DENSE_FACTORIZATIONS[0]
+    rank_deficient = RANK_DEFICIENT[0]
 
     def __new__(cls, wide_band, border_columns, link_rows, iterative_precond="block",
-                sparse_direct="off", dense_factorization="normal-equations"):
+                sparse_direct="off", dense_factorization="normal-equations",
+                rank_deficient="host-svd"):
         self = super().__new__(cls, wide_band, border_columns, link_rows)
         self.iterative_precond = iterative_precond
         self.sparse_direct = sparse_direct
         self.dense_factorization = dense_factorization
+        self.rank_deficient = rank_deficient
         return self
 
     def _replace(self, **changes):
@@ -74,6 +84,8 @@ class Options(collections.namedtuple("Options", "wide_band border_columns link_r
             extra += (self.sparse_direct,)
         if self.dense_factorization != DENSE_FACTORIZATIONS[0]:
             extra += (self.dense_factorization,)
+        if self.rank_deficient != RANK_DEFICIENT[0]:
+            extra += (self.rank_deficient,)
         return tuple(self) + extra
 
 
@@ -121,9 +133,9 @@ def pop_from(options):
     that is not given: the value in force), as the keywords of ``scoped``."""
     held = {name: check(name, options.pop(name, getattr(current(), name)))
             for name in NAMES[:4]}
-    # (``sparse_direct`` and ``dense_factorization`` only when given: without it ``scoped``
-    # leaves the value in force as it is, and the record of a call that does not use it reads
-    # as before the option)
+    # (``sparse_direct``, ``dense_factorization`` and ``rank_deficient`` only when given: without
+    # it ``scoped`` leaves the value in force as it is, and the record of a call that does not
+    # use it reads as before the option)
     for name in NAMES[4:]:
         if name in options:
             held[name] = check(name, options.pop(name))
@@ -152,3 +164,4 @@ iterative_precond, iterative_precond_choice, check_iterative_precond = \
 sparse_direct, sparse_direct_choice, check_sparse_direct = _wrappers("sparse_direct")
 dense_factorization, dense_factorization_choice, check_dense_factorization = \
     _wrappers("dense_factorization")
+rank_deficient, rank_deficient_choice, check_rank_deficient = _wrappers("rank_deficient")
