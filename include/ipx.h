@@ -169,6 +169,9 @@ int ipx_fold2(const double *partial, int32_t count, double *red, const double *g
 int ipx_dense_gemv(int64_t m, int64_t n, const double *A, int64_t lda, const double *x,
                    double alpha, const double *diag, double beta, const double *yin,
                    double *yout, double *red, double *ws, void *stream);
+/* y (n) = B' x for a row-major B (m x n, leading dimension ldb), summed in a fixed order. */
+int ipx_dense_gemvt(int64_t m, int64_t n, const double *B, int64_t ldb, const double *x, double *y,
+                    void *stream);
 int64_t ipx_dense_padded(int64_t m);
 int ipx_gram_f64_mfma(int64_t m, int64_t n, const double *A, int64_t lda, double *G,
                       void *stream);
@@ -215,9 +218,6 @@ int ipx_qr_wy(int64_t m, int64_t n, const double *W, const double *tau, double *
               void *stream);
 /* Linv (M x M) <- L^-1 = R^-T, strict upper triangle exactly zero; L is kept. */
 int ipx_qr_tri_inverse(int64_t M, const double *L, double *Linv, void *stream);
-/* y (n) = B' x for a row-major B (m x n, leading dimension ldb), summed in a fixed order. */
-int ipx_dense_gemvt(int64_t m, int64_t n, const double *B, int64_t ldb, const double *x, double *y,
-                    void *stream);
 
 /* ---- column-pivoted Householder QR of A' for a dense row-major A, m <= n (csrc/denseqrp.hip):
  * A' P = Q [R11 R12], the rank r = the number of leading j with |R_jj| > 2^-43 |R_00|.  No row

@@ -1,6 +1,8 @@
 // Dense Jacobian path (BASELINE config 2; reference projections.py:175-233
 // uses LAPACK pivoted QR).  On MI355X:
 //   * y = A x             : one wave per row, coalesced along the row (HBM-bound)
+//   * y = B' x            : 64 columns per workgroup, no transposed copy (the block products
+//                           of the QR projectors, ipsolver/dense_qr.py, dense_cod.py)
 //   * G = A A'            : fp64 MFMA (v_mfma_f64_16x16x4_f64), the only
 //                           matmul-shaped op of the path
 //   * G = L L', G^-1      : blocked right-looking Cholesky and a blocked
@@ -591,6 +593,31 @@ k_xtx64(const double *G, int M, int nb, double *Y) {
   });
 }
 
+// y[k] = sum_{r < m} B[r][k] x[r], k < n: 64 columns per workgroup, wave g sums the rows
+// g, g + 4, ... in that order, the four sums are added in wave order.
+__global__ void __launch_bounds__(IPX_BLOCK)
+k_dense_gemvt(int m, int n, const double *__restrict__ B, int64_t ldb,
+              const double *__restrict__ x, double *__restrict__ y) {
+  __shared__ double part[IPX_BLOCK / IPX_WAVE][IPX_WAVE];
+  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int k = blockIdx.x * IPX_WAVE + lane;
+  double s = 0.0;
+  if (k < n) {
+    int r = g;
+    for (; r + 12 < m; r += 16) {
+      double b[4], xv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { b[u] = B[(int64_t)(r + 4 * u) * ldb + k]; xv[u] = x[r + 4 * u]; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s += b[u] * xv[u];
+    }
+    for (; r < m; r += 4) s += B[(int64_t)r * ldb + k] * x[r];
+  }
+  part[g][lane] = s;
+  __syncthreads();
+  if (g == 0 && k < n) y[k] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+}
+
 }  // namespace
 
 int ipx_dense_gemv_launch(int m, int n, const double *A, int64_t lda, const double *x,
@@ -634,6 +661,18 @@ int ipx_dense_gemv(int64_t m, int64_t n, const double *A, int64_t lda, const dou
     hipLaunchKernelGGL(k_fold2, dim3(1), dim3(IPX_BLOCK), 0, (hipStream_t)stream, ws, np, red);
     IPX_CHECK_LAUNCH();
   }
+  return IPX_OK;
+}
+
+// y (n) = B' x for a row-major B (m x n, leading dimension ldb): the transposed product of
+// ipx_dense_gemv without a transposed copy, coalesced along n, summed in a fixed order.
+int ipx_dense_gemvt(int64_t m, int64_t n, const double *B, int64_t ldb, const double *x, double *y,
+                    void *stream) {
+  if (m < 0 || n < 0 || !B || !x || !y || ldb < n) return IPX_EINVAL;
+  if (n == 0) return IPX_OK;
+  hipLaunchKernelGGL(k_dense_gemvt, dim3((unsigned)((n + IPX_WAVE - 1) / IPX_WAVE)),
+                     dim3(IPX_BLOCK), 0, (hipStream_t)stream, (int)m, (int)n, B, ldb, x, y);
+  IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
 

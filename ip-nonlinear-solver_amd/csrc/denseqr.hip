@@ -30,14 +30,14 @@
 // + 2 (nt - 1) (trailing) + 3 (set-up, pivot ratio) for ipx_qr_factor, 4 nt + 1 for
 // ipx_qr_form_q.  Norms are plain sums of squares: entries beyond about 1e+-150 are out of
 // scope.
-#include "ipx_common.h"
+// The chunk geometry, the reflector (dlarfg) and the guarded chunk loads / stores of k_qr_panel
+// are qr_common.h's, shared with the pivoted factorization of csrc/denseqrp.hip.
 #include "mfma_tile.h"
+#include "qr_common.h"
 
 namespace {
 
 constexpr int QB = GT;           // panel width = tile edge
-constexpr int QCH = 512;         // columns of the panel rows per workgroup of k_qr_panel
-constexpr int QU = QCH / IPX_WAVE;
 constexpr int QTILE = QB * QB;
 constexpr int QSPLIT_MAX = 16;
 constexpr int QUNITS = 256;      // split-K units aimed at (one per CU)
@@ -92,9 +92,10 @@ k_qr_panel(double *__restrict__ W, int N, int j0, int jb, int j, int jn, int c0,
   __shared__ double s_p[QB];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = c0 + blockIdx.x;
-  const int kbase = c * QCH + lane;
+  const int kbase = c * QR_CHUNK + lane;
   const int j1 = j0 + jb;
-  double beta = 0.0, tj = 0.0, inv = 0.0, tv = 0.0;
+  double tj = 0.0;
+  QrReflector h{0.0, 0.0, 0.0};
   if (j >= 0) {
     if (tid < QB) {
       double t = 0.0;
@@ -104,32 +105,19 @@ k_qr_panel(double *__restrict__ W, int N, int j0, int jb, int j, int jn, int c0,
       s_p[tid] = (j0 + tid >= j && j0 + tid < j1) ? pvin[tid] : 0.0;
     }
     __syncthreads();
-    const double alpha = s_p[j - j0];
     tj = s_t[j - j0];
-    beta = alpha;
-    if (tj != 0.0) {                               // (dlarfg; a zero tail: H = I, tau = 0)
-      beta = -copysign(sqrt(alpha * alpha + tj), alpha);
-      tv = (beta - alpha) / beta;
-      inv = 1.0 / (alpha - beta);
-    }
-    if (blockIdx.x == 0 && tid == 0) tau[j] = tv;
+    h = qr_dlarfg(s_p[j - j0], tj);
+    if (blockIdx.x == 0 && tid == 0) tau[j] = h.tau;
   }
+  const double beta = h.beta, tv = h.tau, inv = h.inv;
   // everything other waves are about to overwrite is read first: row j (the reflector), row jn
-  double v[QU], a[QU];
-#pragma unroll
-  for (int u = 0; u < QU; ++u) {
-    const int k = kbase + u * IPX_WAVE;
-    v[u] = 0.0;
-    a[u] = 0.0;
-    if (k < N) {
-      if (j >= 0) v[u] = k > j ? W[(int64_t)j * N + k] * inv : (k == j ? 1.0 : 0.0);
-      if (jn >= 0) a[u] = W[(int64_t)jn * N + k];
-    }
-  }
+  double v[QR_U] = {}, a[QR_U] = {};
+  if (j >= 0) qr_reflector_chunk(W + (int64_t)j * N, kbase, j, N, inv, v);
+  if (jn >= 0) qr_load_chunk(W + (int64_t)jn * N, kbase, N, a);
   __syncthreads();
   if (j >= 0 && wave == 0) {
 #pragma unroll
-    for (int u = 0; u < QU; ++u) {
+    for (int u = 0; u < QR_U; ++u) {
       const int k = kbase + u * IPX_WAVE;
       if (k < N && k >= j && tj != 0.0) W[(int64_t)j * N + k] = k == j ? beta : v[u];
     }
@@ -139,47 +127,31 @@ k_qr_panel(double *__restrict__ W, int N, int j0, int jb, int j, int jn, int c0,
   if (j >= 0 && jn >= 0) {
     const double w = tv * (s_p[jn - j0] + s_t[jn - j0] * inv);
 #pragma unroll
-    for (int u = 0; u < QU; ++u) a[u] -= w * v[u];
+    for (int u = 0; u < QR_U; ++u) a[u] -= w * v[u];
   }
   // (a wave's rows are a chain of load - update - store - reduce steps: the loads of its next
   // row are issued before the arithmetic of the current one, which the compiler cannot do
   // across the stores)
-  double xn[QU];
-#pragma unroll
-  for (int u = 0; u < QU; ++u) {
-    const int k = kbase + u * IPX_WAVE;
-    xn[u] = (first < j1 && first != jn && k < N) ? W[(int64_t)first * N + k] : 0.0;
-  }
+  double xn[QR_U] = {};
+  if (first < j1 && first != jn) qr_load_chunk(W + (int64_t)first * N, kbase, N, xn);
   for (int i = first; i < j1; i += IPX_BLOCK / IPX_WAVE) {
-    double x[QU];
+    double x[QR_U];
 #pragma unroll
-    for (int u = 0; u < QU; ++u) x[u] = i == jn ? a[u] : xn[u];
+    for (int u = 0; u < QR_U; ++u) x[u] = i == jn ? a[u] : xn[u];
     const int inext = i + IPX_BLOCK / IPX_WAVE;      // (never row jn: that is the first row)
-    if (inext < j1) {
-#pragma unroll
-      for (int u = 0; u < QU; ++u) {
-        const int k = kbase + u * IPX_WAVE;
-        xn[u] = k < N ? W[(int64_t)inext * N + k] : 0.0;
-      }
-    }
+    if (inext < j1) qr_load_chunk(W + (int64_t)inext * N, kbase, N, xn);
     if (i != jn) {
       if (j >= 0) {
         const double w = tv * (s_p[i - j0] + s_t[i - j0] * inv);
 #pragma unroll
-        for (int u = 0; u < QU; ++u) x[u] -= w * v[u];
+        for (int u = 0; u < QR_U; ++u) x[u] -= w * v[u];
       }
     }
-    if (j >= 0 && tv != 0.0) {
-#pragma unroll
-      for (int u = 0; u < QU; ++u) {
-        const int k = kbase + u * IPX_WAVE;
-        if (k < N && k >= j) W[(int64_t)i * N + k] = x[u];
-      }
-    }
+    if (j >= 0 && tv != 0.0) qr_store_chunk(W + (int64_t)i * N, kbase, j, N, x);
     if (jn >= 0) {
       double s = 0.0;
 #pragma unroll
-      for (int u = 0; u < QU; ++u) {
+      for (int u = 0; u < QR_U; ++u) {
         const int k = kbase + u * IPX_WAVE;
         if (k > jn) s += a[u] * x[u];
         if (k == jn) pvout[i - j0] = x[u];
@@ -312,31 +284,6 @@ k_qr_clear_upper(int M, double *__restrict__ G) {
   if ((int)(e % M) > (int)(e / M)) G[e] = 0.0;
 }
 
-// y[k] = sum_{r < m} B[r][k] x[r], k < n: 64 columns per workgroup, wave g sums the rows
-// g, g + 4, ... in that order, the four sums are added in wave order.
-__global__ void __launch_bounds__(IPX_BLOCK)
-k_dense_gemvt(int m, int n, const double *__restrict__ B, int64_t ldb,
-              const double *__restrict__ x, double *__restrict__ y) {
-  __shared__ double part[IPX_BLOCK / IPX_WAVE][IPX_WAVE];
-  const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int k = blockIdx.x * IPX_WAVE + lane;
-  double s = 0.0;
-  if (k < n) {
-    int r = g;
-    for (; r + 12 < m; r += 16) {
-      double b[4], xv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { b[u] = B[(int64_t)(r + 4 * u) * ldb + k]; xv[u] = x[r + 4 * u]; }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += b[u] * xv[u];
-    }
-    for (; r < m; r += 4) s += B[(int64_t)r * ldb + k] * x[r];
-  }
-  part[g][lane] = s;
-  __syncthreads();
-  if (g == 0 && k < n) y[k] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
-}
-
 int qr_splits(int tiles, int K) {
   int s = QUNITS / tiles;
   if (s > QSPLIT_MAX) s = QSPLIT_MAX;
@@ -348,7 +295,7 @@ int qr_splits(int tiles, int K) {
 struct QrWs {
   int64_t part, piv, xv, wk, wt, total;
   QrWs(int64_t M, int64_t N) {
-    const int64_t nt = M / QB, nch = (N + QCH - 1) / QCH;
+    const int64_t nt = M / QB, nch = qr_chunks(N);
     part = 0;
     piv = part + 2 * nch * QB;
     xv = piv + 2 * QB;
@@ -366,7 +313,7 @@ int qr_xv(const double *X0, int64_t ldx, const double *V0, int64_t ldv, int K, i
                      tiles, splits, ws + o.xv);
   IPX_CHECK_LAUNCH();
   const int64_t tot = (int64_t)tiles * QTILE;
-  hipLaunchKernelGGL(k_qr_reduce, dim3((unsigned)((tot + IPX_BLOCK - 1) / IPX_BLOCK)),
+  hipLaunchKernelGGL(k_qr_reduce, dim3(qr_grid(tot)),
                      dim3(IPX_BLOCK), 0, st, ws + o.xv, tiles, splits, ws + o.wk);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
@@ -408,20 +355,20 @@ int ipx_qr_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W,
   if (n > (1 << 30)) return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int M = (int)ipx_dense_padded(m), N = (int)ipx_qr_padded_cols(n);
-  const int nt = M / QB, nch = (N + QCH - 1) / QCH;
+  const int nt = M / QB, nch = qr_chunks(N);
   const QrWs o(M, N);
   const int wpb = IPX_BLOCK / IPX_WAVE;
   hipLaunchKernelGGL(k_qr_copy_in, dim3((M + wpb - 1) / wpb), dim3(IPX_BLOCK), 0, st, (int)m,
                      (int)n, A, lda, W, M, N, info + 1);
   IPX_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_qr_init, dim3((unsigned)(((int64_t)M * M + IPX_BLOCK - 1) / IPX_BLOCK)),
+  hipLaunchKernelGGL(k_qr_init, dim3(qr_grid((int64_t)M * M)),
                      dim3(IPX_BLOCK), 0, st, (int)m, M, L, tau);
   IPX_CHECK_LAUNCH();
   for (int p = 0; p < nt; ++p) {
     const int j0 = p * QB;
     const int jb = (int)m - j0 < QB ? (int)m - j0 : QB;
     if (jb > 0) {
-      const int c0 = j0 / QCH;
+      const int c0 = j0 / QR_CHUNK;
       const dim3 grid(nch - c0), block(IPX_BLOCK);
       double *part[2] = {ws + o.part, ws + o.part + (int64_t)nch * QB};
       double *piv[2] = {ws + o.piv, ws + o.piv + QB};
@@ -486,7 +433,7 @@ int ipx_qr_form_q(int64_t m, int64_t n, const double *W, const double *T, double
   const int M = (int)ipx_dense_padded(m), N = (int)ipx_qr_padded_cols(n);
   const int nt = M / QB;
   const QrWs o(M, N);
-  hipLaunchKernelGGL(k_qr_eye, dim3((unsigned)(((int64_t)M * N + IPX_BLOCK - 1) / IPX_BLOCK)),
+  hipLaunchKernelGGL(k_qr_eye, dim3(qr_grid((int64_t)M * N)),
                      dim3(IPX_BLOCK), 0, st, (int)m, M, N, QT);
   IPX_CHECK_LAUNCH();
   for (int p = nt - 1; p >= 0; --p) {
@@ -514,20 +461,8 @@ int ipx_qr_tri_inverse(int64_t M, const double *L, double *Linv, void *stream) {
     return IPX_ELAUNCH;
   const int rc = ipx_trtri_lower(M, Linv, stream);
   if (rc != IPX_OK) return rc;
-  hipLaunchKernelGGL(k_qr_clear_upper, dim3((unsigned)((M * M + IPX_BLOCK - 1) / IPX_BLOCK)),
+  hipLaunchKernelGGL(k_qr_clear_upper, dim3(qr_grid(M * M)),
                      dim3(IPX_BLOCK), 0, st, (int)M, Linv);
-  IPX_CHECK_LAUNCH();
-  return IPX_OK;
-}
-
-// y (n) = B' x for a row-major B (m x n, leading dimension ldb): the transposed product of
-// ipx_dense_gemv without a transposed copy, coalesced along n, summed in a fixed order.
-int ipx_dense_gemvt(int64_t m, int64_t n, const double *B, int64_t ldb, const double *x, double *y,
-                    void *stream) {
-  if (m < 0 || n < 0 || !B || !x || !y || ldb < n) return IPX_EINVAL;
-  if (n == 0) return IPX_OK;
-  hipLaunchKernelGGL(k_dense_gemvt, dim3((unsigned)((n + IPX_WAVE - 1) / IPX_WAVE)),
-                     dim3(IPX_BLOCK), 0, (hipStream_t)stream, (int)m, (int)n, B, ldb, x, y);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }

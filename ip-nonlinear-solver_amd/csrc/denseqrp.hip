@@ -3,7 +3,8 @@
 // (ipsolver/dense_cod.py), the device exit for rank-deficient dense Jacobians.
 //
 // Layout: csrc/denseqr.hip's.  W is the zero-padded M x N copy of A, row i = column i of A',
-// everything that runs along n is coalesced, a workgroup works on a chunk of 512 columns.
+// everything that runs along n is coalesced, a workgroup works on a chunk of 512 columns
+// (qr_common.h: the geometry, the reflector and the chunk loads / stores of both files).
 //
 // No row is moved.  perm[j] names the row that is pivot j, pos[i] the pivot position of row i
 // (-1: none yet).  Reflector j acts on the coordinates k >= j of every row that is not a pivot
@@ -19,8 +20,8 @@
 //             sqrt(norm2) is |R_jj| up to rounding) -- a failure sets the device words done = 1,
 //             rank = j -- and leaves, for its rows on its chunk, the partial dot products
 //             with the pivot row over k > j and the pivot column W[i][j].
-//   reflect   sums those in chunk order, forms alpha / beta / tau as k_qr_panel does (dlarfg; a
-//             zero tail: tau = 0), applies the reflector to its remaining rows on its chunk and
+//   reflect   sums those in chunk order, forms alpha / beta / tau with k_qr_panel's qr_dlarfg
+//             (qr_common.h; a zero tail: tau = 0), applies the reflector to its remaining rows on its chunk and
 //             leaves their partial squared norms over k > j.
 // The norms are recomputed at every step from the values the update holds in registers anyway:
 // nothing is downdated, so no cancellation safeguard is needed.  All 2 m launches are enqueued
@@ -29,14 +30,10 @@
 //
 // The grid is (chunks, row groups): row i belongs to group i % groups, and every partial is
 // indexed by (chunk, row), so the sums do not depend on the number of groups.
-#include <limits.h>
-
-#include "ipx_common.h"
+#include "qr_common.h"
 
 namespace {
 
-constexpr int PCH = 512;                     // columns per workgroup
-constexpr int PU = PCH / IPX_WAVE;
 constexpr int PWAVES = IPX_BLOCK / IPX_WAVE;
 constexpr int PROWS = 1024;                  // rows per workgroup at most (LDS of k_qrp_reflect)
 constexpr int PUNITS = 512;                  // workgroups aimed at
@@ -54,7 +51,7 @@ struct QrpI {
 struct QrpWs {
   int64_t np, dp, pv, total;
   QrpWs(int64_t M, int64_t N) {
-    const int64_t nch = (N + PCH - 1) / PCH;
+    const int64_t nch = qr_chunks(N);
     np = 0; dp = nch * M; pv = 2 * nch * M; total = pv + M;
   }
 };
@@ -149,10 +146,10 @@ k_qrp_select(const double *__restrict__ W, int N, int m, int M, int j, int c0, i
   if (fail) return;
   // the pivot row on this chunk (k > j), then the dot products of this workgroup's rows with it
   const int c = c0 + blockIdx.x;
-  const int kbase = c * PCH + lane;
-  double a[PU];
+  const int kbase = c * QR_CHUNK + lane;
+  double a[QR_U];
 #pragma unroll
-  for (int u = 0; u < PU; ++u) {
+  for (int u = 0; u < QR_U; ++u) {
     const int k = kbase + u * IPX_WAVE;
     a[u] = (k < N && k > j) ? W[(int64_t)p * N + k] : 0.0;
   }
@@ -162,13 +159,13 @@ k_qrp_select(const double *__restrict__ W, int N, int m, int M, int j, int c0, i
     if (i >= m) break;
     const int ps = pos[i];
     if (ps >= 0 && ps < j) continue;
+    double x[QR_U];
+    qr_load_chunk(W + (int64_t)i * N, kbase, N, x);
     double s = 0.0;
 #pragma unroll
-    for (int u = 0; u < PU; ++u) {
-      const int k = kbase + u * IPX_WAVE;
-      const double x = k < N ? W[(int64_t)i * N + k] : 0.0;
-      s += a[u] * x;
-      if (k == j) pv[i] = x;
+    for (int u = 0; u < QR_U; ++u) {
+      s += a[u] * x[u];
+      if (kbase + u * IPX_WAVE == j) pv[i] = x[u];
     }
     s = ipx_wave_sum(s);
     if (lane == 0) dp[(int64_t)c * M + i] = s;
@@ -186,27 +183,21 @@ k_qrp_reflect(double *__restrict__ W, int N, int m, int M, int j, int c0, int nc
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int groups = gridDim.y;
   const int c = c0 + blockIdx.x;
-  const int kbase = c * PCH + lane;
-  double v[PU];
+  const int kbase = c * QR_CHUNK + lane;
+  double v[QR_U] = {};
   double tv = 0.0;
-#pragma unroll
-  for (int u = 0; u < PU; ++u) v[u] = 0.0;
   if (j >= 0) {
     const int p = perm[j];
     double tj = 0.0;
 #pragma unroll 4
     for (int cc = c0; cc < nch; ++cc) tj += dp[(int64_t)cc * M + p];
-    const double alpha = pv[p];
-    double beta = alpha, inv = 0.0;
-    if (tj != 0.0) {                                 // (dlarfg; a zero tail: H = I, tau = 0)
-      beta = -copysign(sqrt(alpha * alpha + tj), alpha);
-      tv = (beta - alpha) / beta;
-      inv = 1.0 / (alpha - beta);
-    }
+    const QrReflector h = qr_dlarfg(pv[p], tj);
+    const double inv = h.inv;
+    tv = h.tau;
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
       const QrpD o(M);
       dw[o.tau + j] = tv;
-      dw[o.diag + j] = beta;
+      dw[o.diag + j] = h.beta;
       dw[o.vinv + j] = inv;
     }
     // the coefficient of v in the update of each of this workgroup's rows
@@ -218,11 +209,7 @@ k_qrp_reflect(double *__restrict__ W, int N, int m, int M, int j, int c0, int nc
       for (int cc = c0; cc < nch; ++cc) t += dp[(int64_t)cc * M + i];
       s_w[li] = tv * (pv[i] + t * inv);
     }
-#pragma unroll
-    for (int u = 0; u < PU; ++u) {
-      const int k = kbase + u * IPX_WAVE;
-      if (k < N) v[u] = k > j ? W[(int64_t)p * N + k] * inv : (k == j ? 1.0 : 0.0);
-    }
+    qr_reflector_chunk(W + (int64_t)p * N, kbase, j, N, inv, v);
     __syncthreads();
   }
   for (int li = wave; li < PROWS; li += PWAVES) {
@@ -230,24 +217,17 @@ k_qrp_reflect(double *__restrict__ W, int N, int m, int M, int j, int c0, int nc
     if (i >= m) break;
     const int ps = pos[i];
     if (ps >= 0 && ps <= j) continue;                // (a pivot row, this step's included)
-    double x[PU];
-#pragma unroll
-    for (int u = 0; u < PU; ++u) {
-      const int k = kbase + u * IPX_WAVE;
-      x[u] = k < N ? W[(int64_t)i * N + k] : 0.0;
-    }
+    double x[QR_U];
+    qr_load_chunk(W + (int64_t)i * N, kbase, N, x);
     if (j >= 0 && tv != 0.0) {
       const double w = s_w[li];
 #pragma unroll
-      for (int u = 0; u < PU; ++u) {
-        const int k = kbase + u * IPX_WAVE;
-        x[u] -= w * v[u];
-        if (k < N && k >= j) W[(int64_t)i * N + k] = x[u];
-      }
+      for (int u = 0; u < QR_U; ++u) x[u] -= w * v[u];
+      qr_store_chunk(W + (int64_t)i * N, kbase, j, N, x);
     }
     double s = 0.0;
 #pragma unroll
-    for (int u = 0; u < PU; ++u) {
+    for (int u = 0; u < QR_U; ++u) {
       const int k = kbase + u * IPX_WAVE;
       if (k > j) s += x[u] * x[u];
     }
@@ -319,8 +299,6 @@ k_qrp_fold_columns(int rows, int m, int64_t ld, const double *__restrict__ in,
   out[(int64_t)row * ld + perm[cpos]] = in[(int64_t)row * ld + cpos];
 }
 
-unsigned qrp_blocks(int64_t elements) { return (unsigned)((elements + IPX_BLOCK - 1) / IPX_BLOCK); }
-
 }  // namespace
 
 extern "C" {
@@ -344,13 +322,13 @@ int ipx_qrp_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W
   if (n > (1 << 30)) return IPX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int M = (int)ipx_dense_padded(m), N = (int)ipx_qr_padded_cols(n);
-  const int nch = (N + PCH - 1) / PCH;
+  const int nch = qr_chunks(N);
   const int groups = qrp_groups(M, nch);
   const QrpWs o(M, N);
   const QrpD od(M);
   const QrpI oi(M);
   int *perm = iw + oi.perm, *pos = iw + oi.pos, *state = iw + oi.state;
-  hipLaunchKernelGGL(k_qrp_copy_in, dim3(qrp_blocks((int64_t)M * N)), dim3(IPX_BLOCK), 0, st, (int)m,
+  hipLaunchKernelGGL(k_qrp_copy_in, dim3(qr_grid((int64_t)M * N)), dim3(IPX_BLOCK), 0, st, (int)m,
                      (int)n, A, lda, W, M, N, dw, (int *)iw);
   IPX_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_qrp_reflect, dim3(nch, groups), dim3(IPX_BLOCK), 0, st, W, N, (int)m, M, -1,
@@ -358,7 +336,7 @@ int ipx_qrp_factor(int64_t m, int64_t n, const double *A, int64_t lda, double *W
                      (const int *)perm, (const int *)pos, (const int *)state);
   IPX_CHECK_LAUNCH();
   for (int j = 0; j < (int)m; ++j) {
-    const int c0 = j / PCH;
+    const int c0 = j / QR_CHUNK;
     const dim3 grid(nch - c0, groups), block(IPX_BLOCK);
     hipLaunchKernelGGL(k_qrp_select, grid, block, 0, st, (const double *)W, N, (int)m, M, j, c0, nch,
                        (const double *)(ws + o.np), ws + o.dp, ws + o.pv, dw + od.dn, perm, pos,
@@ -381,7 +359,7 @@ int ipx_qrp_reflectors(int64_t m, int64_t n, int64_t r, const double *W, const d
   if (m < 1 || n < m || r < 1 || r > m || !W || !dw || !iw || !Vp || !taup) return IPX_EINVAL;
   const int M = (int)ipx_dense_padded(m), N = (int)ipx_qr_padded_cols(n);
   const int Mr = (int)ipx_dense_padded(r);
-  hipLaunchKernelGGL(k_qrp_reflectors, dim3(qrp_blocks((int64_t)Mr * N)), dim3(IPX_BLOCK), 0,
+  hipLaunchKernelGGL(k_qrp_reflectors, dim3(qr_grid((int64_t)Mr * N)), dim3(IPX_BLOCK), 0,
                      (hipStream_t)stream, (int)r, Mr, N, M, W, dw, (const int *)iw, Vp, taup);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
@@ -392,7 +370,7 @@ int ipx_qrp_write_t(int64_t m, int64_t n, int64_t r, const double *W, const doub
                     const int32_t *iw, double *T, int64_t ldt, void *stream) {
   if (m < 1 || n < m || r < 1 || r > m || !W || !dw || !iw || !T || ldt < m) return IPX_EINVAL;
   const int M = (int)ipx_dense_padded(m), N = (int)ipx_qr_padded_cols(n);
-  hipLaunchKernelGGL(k_qrp_write_t, dim3(qrp_blocks(r * m)), dim3(IPX_BLOCK), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_qrp_write_t, dim3(qr_grid(r * m)), dim3(IPX_BLOCK), 0, (hipStream_t)stream,
                      (int)r, (int)m, N, M, W, dw, (const int *)iw, T, ldt);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
@@ -403,7 +381,7 @@ int ipx_qrp_write_t(int64_t m, int64_t n, int64_t r, const double *W, const doub
 int ipx_qrp_fold_columns(int64_t rows, int64_t m, int64_t ld, const double *in, const int32_t *perm,
                          double *out, void *stream) {
   if (rows < 1 || m < 1 || ld < m || !in || !perm || !out || in == out) return IPX_EINVAL;
-  hipLaunchKernelGGL(k_qrp_fold_columns, dim3(qrp_blocks(rows * m)), dim3(IPX_BLOCK), 0,
+  hipLaunchKernelGGL(k_qrp_fold_columns, dim3(qr_grid(rows * m)), dim3(IPX_BLOCK), 0,
                      (hipStream_t)stream, (int)rows, (int)m, ld, in, (const int *)perm, out);
   IPX_CHECK_LAUNCH();
   return IPX_OK;

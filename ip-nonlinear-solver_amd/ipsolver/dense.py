@@ -86,6 +86,22 @@ class DeviceDense:
         return dv.norm(DVec(self.t.reshape(-1)))
 
 
+def block_gemv(B, ldb, rows, cols, x):
+    """``B[:rows, :cols] x`` for the leading block of a row-major device tensor ``B`` (leading
+    dimension ``ldb``: the padded factors of dense_qr.py / dense_cod.py)."""
+    out = DVec(dv._empty(rows))
+    _hip.call("ipx_dense_gemv", rows, cols, _p(B), ldb, _p(x.t), 1.0, None, 0.0, None,
+              _p(out.t), None, None, stream_ptr())
+    return out
+
+
+def block_gemvt(B, ldb, rows, cols, x):
+    """``B[:rows, :cols]' x`` without a transposed copy."""
+    out = DVec(dv._empty(cols))
+    _hip.call("ipx_dense_gemvt", rows, cols, _p(B), ldb, _p(x.t), _p(out.t), stream_ptr())
+    return out
+
+
 class AugmentedDense(DeviceDense):
     """The barrier's augmented Jacobian ``A = [[J_eq, 0], [J_ineq, diag(s)]]`` assembled from a
     device-mode dense canonical Jacobian (``device_mode.DenseStack``).  Its normal matrix is

@@ -31,15 +31,15 @@ import numpy as np
 import torch
 
 from . import _hip
-from . import device as dv
+from .dense import block_gemv, block_gemvt
+from .dense_qr import HouseholderQR
 from .device import DVec, _p, stream_ptr, ctx
+from .factored_projector import FactoredProjector
 
 _F64 = torch.float64
 
-PIVOT_RTOL = 2.0 ** -43
 
-
-class DenseCODProjector:
+class DenseCODProjector(FactoredProjector):
     """Z, LS, Y for a ``DeviceDense`` A (m x n, 1 <= m <= n) of any rank.
 
     ``rank``; ``pivot_gap``: ``(|R_{r-1,r-1}|, |R_rr|) / |R_00|``, the last kept and the first
@@ -52,10 +52,7 @@ class DenseCODProjector:
         m, n = A.shape
         if m < 1 or m > n:
             raise np.linalg.LinAlgError("Singular Jacobian matrix: %d rows, %d columns" % (m, n))
-        self.A = A
-        self.m, self.n = m, n
-        self.orth_tol, self.max_refin = orth_tol, max_refin
-        self.stats = {"solves": 0, "refinements": 0}
+        FactoredProjector.__init__(self, A, orth_tol, max_refin)
         M, N = int(lib.ipx_dense_padded(m)), int(lib.ipx_qr_padded_cols(n))
         self.M, self.N = M, N
         dev = ctx().device
@@ -68,7 +65,7 @@ class DenseCODProjector:
         done, r = self._iw[2 * M:2 * M + 2].tolist()          # (the one blocking read)
         self.rank = r = int(r)
         assert 0 <= r <= m and (done != 0) == (r < m), (done, r, m)
-        self.norm_A = A.frobenius_norm()
+        self._measure_norm_A()
         del ws
         if r == 0:
             return
@@ -88,25 +85,12 @@ class DenseCODProjector:
         R = torch.empty((r, m), dtype=_F64, device=dev)
         _hip.call("ipx_qrp_write_t", m, n, r, _p(W), _p(self._dw), _p(self._iw), _p(R), m, st)
         del W, Vp, T1, ws
-        N2 = int(lib.ipx_qr_padded_cols(m))
-        self.N2 = N2
-        W2 = torch.empty((Mr, N2), dtype=_F64, device=dev)
-        L2 = torch.empty((Mr, Mr), dtype=_F64, device=dev)
-        T2 = torch.empty((Mr // 64, 64, 64), dtype=_F64, device=dev)
-        tau2 = torch.empty(Mr, dtype=_F64, device=dev)
-        info2 = torch.empty(Mr + 1, dtype=_F64, device=dev)
-        ws = torch.empty(int(lib.ipx_qr_ws_doubles(r, m)), dtype=_F64, device=dev)
-        _hip.call("ipx_qr_factor", r, m, _p(R), m, _p(W2), _p(L2), _p(T2), _p(tau2), _p(info2),
-                  _p(ws), st)
-        Q2T = torch.empty((Mr, N2), dtype=_F64, device=dev)
-        _hip.call("ipx_qr_form_q", r, m, _p(W2), _p(T2), _p(Q2T), _p(ws), st)
+        qr2 = HouseholderQR(R, r, m, m).form()          # (its pivot ratio is never read)
+        self.N2 = N2 = qr2.N
         # Q2' P': the permutation folded into the columns, once
         Q2TP = torch.zeros((Mr, N2), dtype=_F64, device=dev)
-        _hip.call("ipx_qrp_fold_columns", r, m, N2, _p(Q2T), _p(self._iw), _p(Q2TP), st)
-        L2inv = torch.empty((Mr, Mr), dtype=_F64, device=dev)      # R2^-T
-        _hip.call("ipx_qr_tri_inverse", Mr, _p(L2), _p(L2inv), st)
-        del W2, T2, tau2, info2, ws, Q2T, L2
-        self._R, self._Q1T, self._Q2TP, self._L2inv = R, Q1T, Q2TP, L2inv
+        _hip.call("ipx_qrp_fold_columns", r, m, N2, _p(qr2.QT), _p(self._iw), _p(Q2TP), st)
+        self._R, self._Q1T, self._Q2TP, self._L2inv = R, Q1T, Q2TP, qr2.Linv    # (R2^-T)
 
     # -- what the tests read back
     def perm_host(self):
@@ -134,64 +118,21 @@ class DenseCODProjector:
         diag, norms = np.abs(dw[M:M + r]), dw[3 * M:3 * M + r + 1]
         return (float(diag[r - 1] / diag[0]), float(norms[r] / diag[0]) if r < self.m else 0.0)
 
-    # -- device products (dense_qr.py's)
-    def _gemv(self, B, ldb, rows, cols, x):
-        """B[:rows, :cols] x"""
-        out = DVec(dv._empty(rows))
-        _hip.call("ipx_dense_gemv", rows, cols, _p(B), ldb, _p(x.t), 1.0, None, 0.0, None,
-                  _p(out.t), None, None, stream_ptr())
-        return out
-
-    def _gemvt(self, B, ldb, rows, cols, x):
-        """B[:rows, :cols]' x"""
-        out = DVec(dv._empty(cols))
-        _hip.call("ipx_dense_gemvt", rows, cols, _p(B), ldb, _p(x.t), _p(out.t), stream_ptr())
-        return out
-
     def _apply_inv(self, x):
         """pinv(A') x = P Q2 R2^-T Q1' x"""
         self.stats["solves"] += 1
         r = self.rank
         if r == 0:
             return DVec.zeros(self.m)
-        aux1 = self._gemv(self._Q1T, self.N, r, self.n, x)
-        aux2 = self._gemv(self._L2inv, self.Mr, r, r, aux1)
-        return self._gemvt(self._Q2TP, self.N2, r, self.m, aux2)
-
-    def _orth(self, z):
-        norm_z = dv.norm(z)
-        if norm_z == 0 or self.norm_A == 0:
-            return 0.0
-        return dv.norm(self.A.dot(z)) / (self.norm_A * norm_z)
-
-    def null_space(self, x):                                        # projections.py:248-270
-        z = self.A.rmatvec_sub(self._apply_inv(x), x)
-        k = 0
-        while self._orth(z) > self.orth_tol:
-            if k >= self.max_refin:
-                break
-            z = self.A.rmatvec_sub(self._apply_inv(z), z)
-            k += 1
-            self.stats["refinements"] += 1
-        return z
-
-    def least_squares(self, x):                                     # :273-278
-        return self._apply_inv(x)
+        aux1 = block_gemv(self._Q1T, self.N, r, self.n, x)
+        aux2 = block_gemv(self._L2inv, self.Mr, r, r, aux1)
+        return block_gemvt(self._Q2TP, self.N2, r, self.m, aux2)
 
     def row_space(self, x):                                         # :281-286
         """pinv(A) b = Q1 R2^-1 Q2' P' b"""
         r = self.rank
         if r == 0:
             return DVec.zeros(self.n)
-        aux1 = self._gemv(self._Q2TP, self.N2, r, self.m, x)
-        aux2 = self._gemvt(self._L2inv, self.Mr, r, r, aux1)
-        return self._gemvt(self._Q1T, self.N, r, self.n, aux2)
-
-    def operators(self):
-        from .projector import _Op
-        ops = (_Op((self.n, self.n), self.null_space),
-               _Op((self.m, self.n), self.least_squares),
-               _Op((self.n, self.m), self.row_space))
-        for op in ops:
-            op.projector = self
-        return ops
+        aux1 = block_gemv(self._Q2TP, self.N2, r, self.m, x)
+        aux2 = block_gemvt(self._L2inv, self.Mr, r, r, aux1)
+        return block_gemvt(self._Q1T, self.N, r, self.n, aux2)

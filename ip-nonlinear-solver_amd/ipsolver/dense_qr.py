@@ -28,117 +28,95 @@ import numpy as np
 import torch
 
 from . import _hip
-from . import device as dv
-from .device import DVec, _p, stream_ptr, ctx
+from .dense import block_gemv, block_gemvt
+from .device import _p, stream_ptr, ctx
+from .factored_projector import FactoredProjector
 
 _F64 = torch.float64
 
-PIVOT_RTOL = 2.0 ** -43
+PIVOT_RTOL = 2.0 ** -43          # IPX_PIVOT_RTOL (csrc/ipx_common.h)
 
 
-class DenseQRProjector:
+class HouseholderQR:
+    """``B' = Q R`` for a row-major device tensor ``t`` holding ``B`` (m x n, 1 <= m <= n, leading
+    dimension ``lda``).  The constructor enqueues ``ipx_qr_factor``; ``form()`` enqueues ``Q'`` and
+    ``R^-T`` and frees the reflectors.  Afterwards: ``QT`` (M x N, row j = column j of Q), ``L`` =
+    ``R'`` and ``Linv`` = ``R^-T`` (M x M, lower triangular), M / N = m / n rounded up to 64.
+    Device memory while factoring: the padded copy of B that becomes the reflectors and ``QT``
+    (both M x N doubles) and the two triangles."""
+
+    def __init__(self, t, m, n, lda):
+        lib = _hip.load()
+        self.m, self.n = m, n
+        self.M, self.N = M, N = int(lib.ipx_dense_padded(m)), int(lib.ipx_qr_padded_cols(n))
+        dev = ctx().device
+        self._W = torch.empty((M, N), dtype=_F64, device=dev)
+        self.L = torch.empty((M, M), dtype=_F64, device=dev)
+        self._T = torch.empty((M // 64, 64, 64), dtype=_F64, device=dev)
+        tau = torch.empty(M, dtype=_F64, device=dev)
+        self._info = torch.empty(M + 1, dtype=_F64, device=dev)
+        self._ws = torch.empty(int(lib.ipx_qr_ws_doubles(m, n)), dtype=_F64, device=dev)
+        _hip.call("ipx_qr_factor", m, n, _p(t), lda, _p(self._W), _p(self.L), _p(self._T), _p(tau),
+                  _p(self._info), _p(self._ws), stream_ptr())
+        self._pivot_ratio = None
+
+    @property
+    def pivot_ratio(self):
+        """``min_j |R_jj| / ||row j of B||`` (0 for a zero row): a blocking read on first use."""
+        if self._pivot_ratio is None:
+            self._pivot_ratio = float(self._info[0].item())
+        return self._pivot_ratio
+
+    def form(self):
+        st = stream_ptr()
+        self.QT = torch.empty((self.M, self.N), dtype=_F64, device=self.L.device)
+        _hip.call("ipx_qr_form_q", self.m, self.n, _p(self._W), _p(self._T), _p(self.QT),
+                  _p(self._ws), st)
+        self.Linv = torch.empty_like(self.L)
+        _hip.call("ipx_qr_tri_inverse", self.M, _p(self.L), _p(self.Linv), st)
+        del self._W, self._T, self._ws                  # the reflectors are not needed again
+        return self
+
+
+class DenseQRProjector(FactoredProjector):
     """Z, LS, Y for a ``DeviceDense`` A (m x n, 1 <= m <= n) from ``A' = Q R``.
 
     ``pivot_ratio``: ``min_j |R_jj| / ||row j of A||`` (0 for a zero row).  ``stats`` counts
     triangular solves and the refinement steps of ``null_space``; LS and Y take none.
-    Device memory while factoring: the padded copy of A that becomes the reflectors, ``Q'``
-    (both ``M x N`` doubles, M / N = m / n rounded up to 64) and two ``M x M`` triangles; the
-    reflectors are freed once ``Q'`` is formed.
     """
 
     def __init__(self, A, orth_tol=1e-12, max_refin=3):
-        lib = _hip.load()
+        FactoredProjector.__init__(self, A, orth_tol, max_refin)
         m, n = A.shape
-        self.A = A
-        self.m, self.n = m, n
-        self.orth_tol, self.max_refin = orth_tol, max_refin
-        self.stats = {"solves": 0, "refinements": 0}
         if m < 1 or m > n:
             raise np.linalg.LinAlgError("Singular Jacobian matrix: %d rows, %d columns" % (m, n))
-        M, N = int(lib.ipx_dense_padded(m)), int(lib.ipx_qr_padded_cols(n))
-        self.M, self.N = M, N
-        dev = ctx().device
-        st = stream_ptr()
-        W = torch.empty((M, N), dtype=_F64, device=dev)
-        L = torch.empty((M, M), dtype=_F64, device=dev)
-        T = torch.empty((M // 64, 64, 64), dtype=_F64, device=dev)
-        tau = torch.empty(M, dtype=_F64, device=dev)
-        info = torch.empty(M + 1, dtype=_F64, device=dev)
-        ws = torch.empty(int(lib.ipx_qr_ws_doubles(m, n)), dtype=_F64, device=dev)
-        _hip.call("ipx_qr_factor", m, n, _p(A.t), n, _p(W), _p(L), _p(T), _p(tau), _p(info),
-                  _p(ws), st)
-        self.pivot_ratio = float(info[0].item())
-        self._L = L                                     # R' (lower triangular, padded)
+        self._qr = qr = HouseholderQR(A.t, m, n, n)
+        self.M, self.N = qr.M, qr.N
+        self.pivot_ratio = qr.pivot_ratio
         if not self.pivot_ratio >= PIVOT_RTOL:
             raise np.linalg.LinAlgError(
                 "numerically rank deficient: min |R_jj| / ||a_j|| = %.3g" % self.pivot_ratio)
-        QT = torch.empty((M, N), dtype=_F64, device=dev)
-        _hip.call("ipx_qr_form_q", m, n, _p(W), _p(T), _p(QT), _p(ws), st)
-        Linv = torch.empty((M, M), dtype=_F64, device=dev)
-        _hip.call("ipx_qr_tri_inverse", M, _p(L), _p(Linv), st)
-        del W, T, ws                                    # the reflectors are not needed again
-        self._QT, self._Linv = QT, Linv
-        self.norm_A = A.frobenius_norm()
+        qr.form()
+        self._measure_norm_A()
 
     # -- what the tests read back
     def Q_host(self):
         """Q (n x m) on the host."""
-        return self._QT[:self.m, :self.n].t().cpu().numpy()
+        return self._qr.QT[:self.m, :self.n].t().cpu().numpy()
 
     def R_host(self):
         """R (m x m, upper triangular) on the host."""
-        return self._L[:self.m, :self.m].t().cpu().numpy()
+        return self._qr.L[:self.m, :self.m].t().cpu().numpy()
 
-    # -- device products
-    def _gemv(self, B, ldb, rows, cols, x):
-        """B[:rows, :cols] x"""
-        out = DVec(dv._empty(rows))
-        _hip.call("ipx_dense_gemv", rows, cols, _p(B), ldb, _p(x.t), 1.0, None, 0.0, None,
-                  _p(out.t), None, None, stream_ptr())
-        return out
-
-    def _gemvt(self, B, ldb, rows, cols, x):
-        """B[:rows, :cols]' x"""
-        out = DVec(dv._empty(cols))
-        _hip.call("ipx_dense_gemvt", rows, cols, _p(B), ldb, _p(x.t), _p(out.t), stream_ptr())
-        return out
-
-    def _solve(self, x):
+    def _apply_inv(self, x):
         """R^-1 Q' x  (projections.py:192-193)"""
         self.stats["solves"] += 1
-        aux1 = self._gemv(self._QT, self.N, self.m, self.n, x)
-        return self._gemvt(self._Linv, self.M, self.m, self.m, aux1)
-
-    def _orth(self, z):
-        norm_z = dv.norm(z)
-        if norm_z == 0 or self.norm_A == 0:
-            return 0.0
-        return dv.norm(self.A.dot(z)) / (self.norm_A * norm_z)
-
-    def null_space(self, x):                                        # :190-212
-        z = self.A.rmatvec_sub(self._solve(x), x)
-        k = 0
-        while self._orth(z) > self.orth_tol:
-            if k >= self.max_refin:
-                break
-            z = self.A.rmatvec_sub(self._solve(z), z)
-            k += 1
-            self.stats["refinements"] += 1
-        return z
-
-    def least_squares(self, x):                                     # :215-221
-        return self._solve(x)
+        qr = self._qr
+        aux1 = block_gemv(qr.QT, qr.N, self.m, self.n, x)
+        return block_gemvt(qr.Linv, qr.M, self.m, self.m, aux1)
 
     def row_space(self, x):                                         # :224-231
         self.stats["solves"] += 1
-        aux2 = self._gemv(self._Linv, self.M, self.m, self.m, x)    # R^-T x
-        return self._gemvt(self._QT, self.N, self.m, self.n, aux2)  # Q aux2
-
-    def operators(self):
-        from .projector import _Op
-        ops = (_Op((self.n, self.n), self.null_space),
-               _Op((self.m, self.n), self.least_squares),
-               _Op((self.n, self.m), self.row_space))
-        for op in ops:
-            op.projector = self
-        return ops
+        qr = self._qr
+        aux2 = block_gemv(qr.Linv, qr.M, self.m, self.m, x)         # R^-T x
+        return block_gemvt(qr.QT, qr.N, self.m, self.n, aux2)       # Q aux2

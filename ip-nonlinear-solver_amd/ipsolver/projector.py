@@ -37,13 +37,15 @@ from . import device as dv
 from . import solver_options
 from .device import DVec, DeviceCSR, _p, stream_ptr, ctx
 from .dense import DenseNormalSolver, DeviceDense
+from .factored_projector import FactoredProjector, _Op, operator_triple  # noqa: F401
 from .dense_qr import DenseQRProjector
 from .dense_cod import DenseCODProjector
 from .device_mode import RowSelection
 # The solvers, their selection and its options live in modules of their own, layered
 #   solver_options < banded < blocktri, blockwide, iterative, nested < band_solver < bordered
 #   < linked < boxschur < selection < this one;
-# their names stay public here.
+# their names stay public here.  (dense < factored_projector < dense_qr < dense_cod < this one:
+# the operator object ``_Op`` and the refinement loop the factored projectors share.)
 from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link_rows,  # noqa: F401
                              wide_band_policy, border_columns_limit, link_rows_limit,
                              check_wide_band, check_border_columns, check_link_rows,
@@ -79,20 +81,6 @@ def note_solver(ops):
         _last_solver[0] = solver_name(P.solver)
     else:
         _last_solver[0] = None if P is None else type(P).__name__
-
-
-class _Op:
-    """Operator object returned by ``projections`` (duck type of scipy's
-    LinearOperator as used by the reference: shape / dot / matvec)."""
-
-    def __init__(self, shape, fn):
-        self.shape = shape
-        self._fn = fn
-
-    def dot(self, x):
-        return self._fn(x if isinstance(x, DVec) else DVec.from_host(x))
-
-    matvec = dot
 
 
 class NormalEquationProjector:
@@ -235,15 +223,10 @@ class NormalEquationProjector:
         return y
 
     def operators(self):
-        ops = (_Op((self.n, self.n), self.null_space),
-               _Op((self.m, self.n), self.least_squares),
-               _Op((self.n, self.m), self.row_space))
-        for op in ops:
-            op.projector = self      # lets the fused CG loop recognise its own operators
-        return ops
+        return operator_triple(self)
 
 
-class SVDProjector:
+class SVDProjector(FactoredProjector):
     """Z, LS, Y from a thin SVD ``A = U diag(s) Vt`` with the singular values ``<= tol``
     dropped -- the reference's ``svd_factorization_projections`` (projections.py:236-287)
     statement by statement, on device vectors.  Reached for rank-deficient Jacobians (with
@@ -253,8 +236,7 @@ class SVDProjector:
 
     def __init__(self, A, orth_tol, max_refin, tol):
         import scipy.linalg
-        self.A = A
-        self.m, self.n = A.shape
+        FactoredProjector.__init__(self, A, orth_tol, max_refin)
         if self.m * self.n > self.MAX_ELEMENTS:
             raise np.linalg.LinAlgError(
                 "Singular Jacobian matrix (%d x %d): too large for the dense SVD fallback"
@@ -266,9 +248,7 @@ class SVDProjector:
         self.U = DeviceDense.from_host(U[:, keep])
         self.Vt = DeviceDense.from_host(Vt[keep, :])
         self.inv_s = DVec.from_host(1.0 / sv[keep])
-        self.orth_tol, self.max_refin = orth_tol, max_refin
-        self.norm_A = A.frobenius_norm() if self.m > 0 else 0.0
-        self.stats = {"solves": 0, "refinements": 0}
+        self._measure_norm_A()
 
     def _apply_inv(self, x):
         """v = U 1/s V' x = pinv(A') x  (:250-253)"""
@@ -277,38 +257,10 @@ class SVDProjector:
             return DVec.zeros(self.m)
         return self.U.dot(self.inv_s * self.Vt.dot(x))
 
-    def _orth(self, z):
-        norm_z = dv.norm(z)
-        if norm_z == 0 or self.norm_A == 0:
-            return 0.0
-        return dv.norm(self.A.dot(z)) / (self.norm_A * norm_z)
-
-    def null_space(self, x):                                        # :248-270
-        z = self.A.rmatvec_sub(self._apply_inv(x), x)
-        k = 0
-        while self._orth(z) > self.orth_tol:
-            if k >= self.max_refin:
-                break
-            z = self.A.rmatvec_sub(self._apply_inv(z), z)
-            k += 1
-            self.stats["refinements"] += 1
-        return z
-
-    def least_squares(self, x):                                     # :273-278
-        return self._apply_inv(x)
-
     def row_space(self, x):                                         # :281-286
         if self.rank == 0:
             return DVec.zeros(self.n)
         return self.Vt.T.dot(self.inv_s * self.U.T.dot(x))
-
-    def operators(self):
-        ops = (_Op((self.n, self.n), self.null_space),
-               _Op((self.m, self.n), self.least_squares),
-               _Op((self.n, self.m), self.row_space))
-        for op in ops:
-            op.projector = self
-        return ops
 
 
 def orthogonality(A, g):

@@ -49,6 +49,9 @@ Outputs (numbers only -- no reference source travels; an .npz over 1 MiB is writ
   pcr_family_bits.npz  (``--pcr-family``: ON THE GPU, without the reference) what THIS project's
                     cyclic-reduction kernels compute on the cases of tests/pcr_family_cases.py,
                     to the bit; re-recorded only by a change that reorders a sum on purpose
+  dense_qr_bits.npz  (``--dense-qr-bits``: ON THE GPU, without the reference) the same for the
+                    dense QR projectors on the cases of tests/dense_qr_bits_cases.py, with their
+                    launch and blocking-read counts
 """
 import json
 import os
@@ -73,8 +76,21 @@ def pcr_family():
     np.savez_compressed(os.path.join(HERE, "pcr_family_bits.npz"), **out)
 
 
+def dense_qr_bits():
+    """This project's own outputs (needs the GPU and the built library, not the reference)."""
+    for p in (os.path.join(ROOT, "ip-nonlinear-solver_amd"), os.path.join(ROOT, "tests")):
+        sys.path.insert(0, p)
+    import dense_qr_bits_cases
+    path = os.path.join(HERE, "dense_qr_bits.npz")
+    np.savez_compressed(path, **dense_qr_bits_cases.record())
+    assert os.path.getsize(path) < (1 << 20), os.path.getsize(path)
+
+
 if "--pcr-family" in sys.argv:
     pcr_family()
+    sys.exit(0)
+if "--dense-qr-bits" in sys.argv:
+    dense_qr_bits()
     sys.exit(0)
 
 sys.path.insert(0, "/root/reference")
