@@ -474,18 +474,58 @@ typedef struct ipx_cg_args {
    * consecutive columns, as on a banded Jacobian): the fused projection takes the offset as the
    * constant k and does not read A_ell_off16 (which stays bound).  0: the table is read. */
   int32_t A_contig;
+  /* The radius guard: the test of qp_subproblem.py:583 decided from a norm bound while that bound
+   * stays below the radius.  rguard = three doubles of device memory X, Q, T with X >= ||x_k||,
+   * Q >= ||p_k|| in floating point (ipx_rguard_step_x / ipx_rguard_step_q below: the triangle
+   * inequality on x + alpha p and beta p - g, every update inflated by 1 + 2^-20); T is the
+   * bound on ||x_k + alpha p_k|| the projection half of iteration k leaves for its update half.
+   * radius_guard != 0 with rguard bound, where the carried sums (xsums) would apply:
+   * ipx_cg_iterate runs the kernels of the no_radius loop -- x and p are not read by the
+   * projection half, no sums are formed or folded -- plus these scalars on lead lanes; the
+   * priming (ipx_cg_prime, ipx_cg_prime_state_guard) writes X0 and Q0.  A bound that is not
+   * below the radius (or not finite) stops the batch with IPX_CG_STOP_GUARD_LOST and commits
+   * nothing: ipx_cg_guard_resume finishes the iteration in the carried-sum form, and the caller
+   * clears radius_guard for the rest of the call.  0 (or rguard NULL): every launch as
+   * without the field. */
+  double *rguard;
+  int32_t radius_guard;
 } ipx_cg_args;
 /* k_cg_step2_hp mode bits: 1 = no radius / box test, 2 = no orthogonality test (the two
- * ipx_cg_resume and ipx_cg_step2_hp take), 4 = the radius test from the carried sums (set by
- * ipx_cg_iterate alone). */
+ * ipx_cg_resume and ipx_cg_step2_hp take), 4 = the radius test from the carried sums, 8 = from
+ * the radius guard's bound (both set by ipx_cg_iterate alone). */
 #define IPX_CG_MODE_NO_RADIUS 1
 #define IPX_CG_MODE_NO_ORTH 2
 #define IPX_CG_MODE_CARRIED 4
+#define IPX_CG_MODE_GUARD 8
 /* Stop code 10 of the state block: the carried sums could not decide the radius test (inside
  * the band, or their tag is not this iteration's).  Nothing of the iteration's step2 was
  * committed; the host forms ||x + alpha p|| itself and takes the exit of :583 or resumes
  * (ipx_cg_resume, mode 1). */
 #define IPX_CG_STOP_RADIUS_UNDECIDED 10
+/* Stop code 11: the radius guard's bound T on ||x + alpha p|| is not below the radius (or not
+ * finite).  Nothing of the iteration's step2 was committed; ipx_cg_guard_resume takes over. */
+#define IPX_CG_STOP_GUARD_LOST 11
+/* The radius guard's arithmetic, shared by the kernels and the host (a CPU test drives the same
+ * code): ipx_rguard_step_x = (X + |alpha| Q)(1 + 2^-20) >= ||x + alpha p||,
+ * ipx_rguard_step_q = (beta Q + sqrt(gg))(1 + 2^-20) >= ||beta p - g|| with gg = ||g||^2 as the
+ * loop summed it, ipx_rguard_start = sqrt(sumsq)(1 + 2^-20) >= the norm a computed sum of squares
+ * stands for.  The inflation covers the error of a sum of up to 2^31 squares in any order
+ * (<= 2^-22 relative) and the roundings of fl(x + fl(alpha p)), fl(fl(beta p) - g). */
+double ipx_rguard_start(double sumsq);
+double ipx_rguard_step_x(double X, double Q, double alpha);
+double ipx_rguard_step_q(double Q, double beta, double gg);
+/* After stop code 11 on iteration it_stop (the stop word cleared by the caller): the sums of
+ * x^2, x p, p^2 over the current x and p into the carried sums' folded arrays (256 workgroups,
+ * fixed order), then that iteration's update half in the carried-sum form (mode 4, the sums
+ * written), then the folded arrays zeroed again (the loop's launches write only their first
+ * ceil(H_ntiles / 64) entries).  From there the call runs as with radius_guard = 0, the next
+ * batch with xsums_carry = 1 when this launch ends without a stop. */
+int ipx_cg_guard_resume(const ipx_cg_args *a, int32_t it_stop, void *stream);
+/* ipx_cg_prime_state that also writes X0 and Q0 of the radius guard (rguard: three doubles, or
+ * NULL) from ||x0||^2 and rt_g, in the same launch. */
+int ipx_cg_prime_state_guard(double *state, const double *red, const int32_t *idx7, double tol_in,
+                             double radius, double orth_tol, double norm_A, double cancellation,
+                             double *rguard, void *stream);
 int ipx_cg_resident_ok(const ipx_cg_args *a);
 int64_t ipx_cg_resident_ll_words(int32_t nwg, int32_t hw);
 /* the kernel's budgets for the host code that builds its tables: workgroups per launch, threads,

@@ -1819,7 +1819,10 @@ int launch_solve_pcr(const LevDev &lv, int L, const double *w, double *x, double
 // part4 by PcrPairTail's lane-to-variable mapping and pcr_own_residual's -- the same bits.  g goes
 // to a buffer that is not r_in (a neighbour's window still reads the entries this workgroup owns).
 // XN as in k_cg_step1_ar: 0 partials of ||x + alpha p||^2 over the own variables (one per
-// workgroup); 1 not formed; 2 the first `ncomp` workgroups fold a slice of the carried sums.
+// workgroup); 1 not formed; 2 the first `ncomp` workgroups fold a slice of the carried sums;
+// 3 (the radius guard) as 1, and the lead lane, once it has alpha, stores the bound
+// T = (X + |alpha| Q)(1 + 2^-20) on ||x + alpha p|| into the guard's words (J.xs_comp) for
+// k_cg_step2_hp<.., GUARD>.
 // PRIME: the projection alone, for the priming (csrc/cg.hip prime_project_tail): no step -- the
 // span holds r_in itself, no p'Hp fold, no state words read or written, *guard != 0 skips the
 // launch --, g = sign (r_in - A'v) as AtvJob's sign forms it.
@@ -1854,6 +1857,11 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
     stop = J.st[ST_STOP];
     rtg = J.st[J.parity ? ST_RTG1 : ST_RTG0];
     tol = J.st[ST_TOL];
+  }
+  // XN = 3: the guard's X and Q, requested with the state words (the lead lane alone)
+  double rgX = 0.0, rgQ = 0.0;
+  if constexpr (XN == 3) {
+    if (wg == 0 && tid == 0) { rgX = J.xs_comp[IPX_RG_X]; rgQ = J.xs_comp[IPX_RG_Q]; }
   }
   // p'Hp partials: the loads of ipx_fold_regs<1, FU>::load in a workgroup of FW lanes
   double ft[FU];
@@ -1950,6 +1958,7 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
     if (lead) {
       J.st[ST_NITER] += 1.0; J.st[ST_PTHP] = ptHp; J.st[ST_ALPHA] = alpha;
       *J.where = J.dest;
+      if constexpr (XN == 3) J.xs_comp[IPX_RG_T] = ipx_rguard::step_x(rgX, rgQ, alpha);
     }
   }
 #pragma unroll
@@ -2080,6 +2089,10 @@ int launch_step1_solve_tail_qc(const LevDev &lv, int L, const ipx_fused_proj_job
       break;
     case 1:
       hipLaunchKernelGGL((k_step1_solve_tail<QV, 1, false, CONTIG>), grid, block, 0, st, lv.m,
+                         rows_wg, L, nwin, lv.band, J);
+      break;
+    case 3:
+      hipLaunchKernelGGL((k_step1_solve_tail<QV, 3, false, CONTIG>), grid, block, 0, st, lv.m,
                          rows_wg, L, nwin, lv.band, J);
       break;
     default:
@@ -2995,7 +3008,8 @@ int ipx_banded_fused_proj_launch(void *handle, const ipx_fused_proj_job &job, in
       !job.A_ell_val || !job.A_ell_off16 || !job.A_rowfirst || !job.win || !job.vown ||
       !job.ell_row || !job.ell_val || !job.v || !job.part3 || !job.part4 ||
       (job.n & 1) || (job.xn == 0 && (!job.x || !job.p || !job.part2)) ||
-      (job.xn == 2 && (!job.xs_raw || !job.xs_comp || job.nraw < 1)) || job.xn < 0 || job.xn > 2)
+      (job.xn == 2 && (!job.xs_raw || !job.xs_comp || job.nraw < 1)) ||
+      (job.xn == 3 && !job.xs_comp) || job.xn < 0 || job.xn > 3)
     return IPX_EINVAL;
   if (ipx_banded_fused_proj_ok(handle, job.rl, 1, job.qv) != IPX_OK) return IPX_EUNSUPPORTED;
   Banded *h = (Banded *)handle;

@@ -464,6 +464,13 @@ constexpr int FT_NNZ = IPX_SPMV_TILE_NNZ;
 //        the block the fold's loads and the tile's loads are scheduled in: measured +1.5 us).
 //        That kernel has compared the raw partials' tag with `it` and left NaNs where they
 //        are not this iteration's.
+//   The GUARD instantiation (mode bit 8; raw != NULL, write = 0, no mode bit 4) takes the radius
+//        guard's X, Q, T (ipx_cg_args.rguard) in `in`, and writes them: the test of :583 is
+//        !(T < radius) on the bound the projection half of this iteration left; a launch that
+//        commits moves X <- T, Q <- (beta Q + sqrt(gg))(1 + 2^-20) and clears the tag of the
+//        sums it does not renew.  (No field of its own: this struct is part of the argument
+//        segment of EVERY instantiation -- a word more moves their hidden arguments, for this
+//        kernel into another 64-byte line of the segment)
 struct ipx_xsums_job {
   double *raw;
   const double *in;
@@ -488,7 +495,13 @@ constexpr double XS_BAND = 1e-9; // the carried form decides :583 only outside t
 // XSUM: the instantiation that writes and / or consumes the carried sums of the radius test
 // (ipx_xsums_job).  The launcher picks it only for launches that do; every other launch -- the
 // trust_radius = inf loop, the stand-alone entry, BOX, PEER -- runs the kernel without them.
-template <bool HAS_DIAG, int Q, int QS, bool BOX, bool C16, bool PEER, bool XSUM = false>
+// GUARD: the radius guard's instantiation -- the kernel of the trust_radius = inf loop (no
+// ||x + alpha p||^2 partials, no sums, a four-way block sum) that decides :583 from the bound T
+// every workgroup loads with its state words (xs.in: the guard's three words).  Without mode
+// bit 1 a bound that is not below the radius stops the batch (IPX_CG_STOP_GUARD_LOST); with it
+// (a resumed iteration whose test was taken) the bounds advance all the same.
+template <bool HAS_DIAG, int Q, int QS, bool BOX, bool C16, bool PEER, bool XSUM = false,
+          bool GUARD = false>
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict__ p2, int np2,
               const double *__restrict__ p3, int np3, const double *__restrict__ p4, int np4,
@@ -502,6 +515,7 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
               typename peer_arg<PEER>::type pj, double *g_halo, ipx_xsums_job xs) {
   constexpr bool XS = XSUM;                    // the carried sums of the radius test
   static_assert(!XSUM || (!BOX && !PEER), "carried sums: no box, one GPU");
+  static_assert(!GUARD || (!BOX && !PEER && !XSUM), "radius guard: no box, one GPU, no sums");
   // (the folded sums ride in the three loads per lane of the xn2 partials: ipx_fold_regs<2, 3>)
   static_assert(XS_STRIDE == IPX_BLOCK, "one folded entry per lane and load");
   __shared__ double prod[FT_NNZ];
@@ -524,7 +538,8 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   // load u of this lane is its entry of array u)
   const bool carried = XS && (mode & 4) != 0;
   const double *const partsA[2] = {BOX ? p2 + np2 : (carried ? xs.in : p2), p4};
-  const int countsA[2] = {(mode & 1) ? 0 : (carried ? 3 * XS_STRIDE : np2), (mode & 2) ? 0 : np4};
+  const int countsA[2] = {(GUARD || (mode & 1)) ? 0 : (carried ? 3 * XS_STRIDE : np2),
+                          (mode & 2) ? 0 : np4};
   const double *const partsB[1] = {p3};
   const int countsB[1] = {np3};
   const double *const partsC[1] = {BOX ? p2 : p2 + np2};     // BOX: xn2;  else unused (count 0)
@@ -533,6 +548,11 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   const double radius = st[ST_RADIUS], orth_rhs = st[ST_ORTH_RHS];
   const double rtg = st[parity ? ST_RTG1 : ST_RTG0];
   const double alpha = st[ST_ALPHA];
+  double rgT = 0.0, rgQ = 0.0;                 // GUARD: the bound on ||x + alpha p||; Q (lead lane)
+  if constexpr (GUARD) {
+    rgT = xs.in[IPX_RG_T];
+    if (tile == 0 && tid == 0) rgQ = xs.in[IPX_RG_Q];
+  }
   ipx_fold_regs<2, BOX ? 2 : 3> foldA;         // BOX: {viol, tt}      else {xn2, tt}
   ipx_fold_regs<1, 4> foldB;                   // gg
   ipx_fold_regs<1, BOX ? 2 : 1> foldC;         // BOX: xn2
@@ -662,7 +682,15 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     }
     if (stop != 0.0) return;
   }
-  if (!(mode & 1)) {
+  if constexpr (GUARD) {
+    // :583 from the bound: ||x + alpha p|| <= T < radius -- the test is false.  Anything else
+    // (NaN and inf included) decides nothing here
+    if (!(mode & 1) && !(rgT < radius)) {
+      if (lead) st[ST_STOP] = (double)IPX_CG_STOP_GUARD_LOST;
+      return;
+    }
+  }
+  if (!GUARD && !(mode & 1)) {
     double xn2 = red[0], viol = red[1];
     if (carried) {
       // ||x + alpha p||^2 from the sums over the x and p this iteration started from.  M bounds
@@ -705,6 +733,13 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     st[ST_IT_DONE] += 1.0;
     // x and p change below: tag the sums this launch leaves, or void those it does not renew
     if constexpr (XS) xs.raw[3 * ntiles] = xs.write ? (double)(xs.it + 1) : 0.0;
+    if constexpr (GUARD) {
+      // (no other workgroup of this launch reads X or Q; T was loaded before any store)
+      double *rg = const_cast<double *>(xs.in);
+      rg[IPX_RG_Q] = ipx_rguard::step_q(rgQ, beta, gg);
+      rg[IPX_RG_X] = rgT;
+      xs.raw[3 * ntiles] = 0.0;
+    }
   }
   // p_next on the span (LDS), x_next / p_next / boundary copies on the own rows
   double *pbo = pb_out + (int64_t)tile * 2 * hmax;
@@ -853,6 +888,9 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
 // arrays each (one wave, fixed order), so that every workgroup of the consuming k_cg_step2_hp
 // folds 3 x ncomp entries, not 3 x H_ntiles.  They compare the raw partials' tag with `it` and
 // pass NaNs on when the sums are not this iteration's.
+// XN = 3: the radius guard.  As XN = 1 (no x, no p, no fold, no part2); xs_comp is the guard's
+// three words (ipx_cg_args.rguard: X, Q, T) and the lead lane, once it has alpha, stores
+// T = (X + |alpha| Q)(1 + 2^-20) for k_cg_step2_hp<.., GUARD> of this iteration.
 // C16: column indices as 16-bit offsets into the tile's span (col - own[tile]; the host
 // binding builds them once per pattern), 2 bytes instead of 4 per nonzero.
 // PEER: p1 is the rank's own range of the p'Hp partials; summed over the ranks in the prologue
@@ -924,6 +962,10 @@ k_cg_step1_ar(int n, double *st, int parity, const double *__restrict__ p1, int 
     }
     xtag = xs_raw[3 * nraw];
   }
+  double rgX = 0.0, rgQ = 0.0;                       // XN = 3: the guard's X and Q (lead lane)
+  if constexpr (XN == 3) {
+    if (tile == 0 && tid == 0) { rgX = xs_comp[IPX_RG_X]; rgQ = xs_comp[IPX_RG_Q]; }
+  }
   if (!PEER && stop != 0.0) return;                  // (PEER: see k_cg_step2_hp)
   if (PEER && stop == 7.0) return;
   CG_STAMP(9);
@@ -962,6 +1004,9 @@ k_cg_step1_ar(int n, double *st, int parity, const double *__restrict__ p1, int 
   CG_STAMP(10);
   const double alpha = rtg / ptHp;                   // :579
   if (lead) { st[ST_NITER] += 1.0; st[ST_PTHP] = ptHp; st[ST_ALPHA] = alpha; }
+  if constexpr (XN == 3) {
+    if (lead) xs_comp[IPX_RG_T] = ipx_rguard::step_x(rgX, rgQ, alpha);
+  }
   double sx = 0.0;
 #pragma unroll
   for (int k = 0; k < QS; ++k) {
@@ -1073,6 +1118,42 @@ k_cg_settle_r(int64_t n, const int32_t *__restrict__ where, const double *__rest
 
 // Voids the tag of the carried sums (ipx_cg_args.xsums) on the stream.
 __global__ void k_xsums_void(double *xs_tag) { *xs_tag = 0.0; }
+
+// The radius guard behind an update half that ran as the vector step2 (ipx_cg_resume: the test
+// of :583 was taken and passed before the host's event): when that launch committed (the stop
+// word the caller cleared is still 0) X <- T, Q <- (beta Q + sqrt(gg))(1 + 2^-20) with the beta
+// and the ||g_next||^2 it left in the state block.
+__global__ void k_rguard_advance(const double *__restrict__ st, int parity, double *rg) {
+  if (st[ST_STOP] != 0.0) return;
+  const double gg = st[parity ? ST_RTG0 : ST_RTG1];
+  rg[IPX_RG_Q] = ipx_rguard::step_q(rg[IPX_RG_Q], st[ST_BETA], gg);
+  rg[IPX_RG_X] = rg[IPX_RG_T];
+}
+
+// Losing the radius guard (ipx_cg_guard_resume): sum x^2, sum x p, sum p^2 over the current x
+// and p into the carried sums' three folded arrays (ipx_xsums_job.in), one entry per workgroup
+// and array -- XS_STRIDE workgroups, each over its own run of the vectors, lanes strided within
+// it, the block sum in its fixed order: the same bits on every run.  The order differs from the
+// per-tile one of k_cg_step2_hp; the band of XS_BAND x M around radius^2 covers that.
+__global__ void __launch_bounds__(IPX_BLOCK)
+k_rguard_sums(int64_t n, const double *__restrict__ x, const double *__restrict__ p,
+              double *__restrict__ comp) {
+  __shared__ double lds[3 * (IPX_BLOCK / IPX_WAVE)];
+  const int64_t per = (n + XS_STRIDE - 1) / XS_STRIDE;
+  const int64_t lo = min((int64_t)blockIdx.x * per, n), hi = min(lo + per, n);
+  double acc[3] = {0.0, 0.0, 0.0}, out[3];
+  for (int64_t i = lo + threadIdx.x; i < hi; i += IPX_BLOCK) {
+    const double xv = x[i], pv = p[i];
+    acc[0] += xv * xv;
+    acc[1] += xv * pv;
+    acc[2] += pv * pv;
+  }
+  ipx_block_sum_multi<3>(acc, lds, out);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) comp[q * XS_STRIDE + blockIdx.x] = out[q];
+  }
+}
 
 // Partitioned row-sharded loop (ipsolver/sharded.py): up to four sub-ranges of partial
 // arrays -- the entries produced by a rank's OWN tiles / workgroups -- summed in a fixed
@@ -1223,6 +1304,10 @@ struct LoopPlan {
   // (ipx_cg_args.xsums): both fused kernels (fused step1 implies no box), a finite radius, and
   // enough workgroups in the fused step1 to fold the raw partials
   bool xsums;
+  // ... and is decided from the radius guard's bound instead (ipx_cg_args.rguard, radius_guard):
+  // the launches of no_xn2 with the guard's forms of the two fused kernels; the carried sums
+  // stay bound for the iteration that loses the guard (ipx_cg_guard_resume)
+  bool guard;
   int xs_ncomp;         // folded entries per carried sum: one per XS_SLICE row tiles of H
   // entries per half of part1 .. part4:
   int np1;              // row tiles of a CSR Hessian / workgroups of the dense or low-rank product
@@ -1280,6 +1365,7 @@ LoopPlan plan_of(const ipx_cg_args *a) {
   const int xs_wgs = P.proj == PJ_STEP1_SOLVE_TAIL ? P.np4 : (int)a->A_ntiles;   // who folds them
   P.xsums = a->xsums != nullptr && fused_ar && P.fused_hp && a->no_radius == 0 &&
             P.xs_ncomp <= xs_wgs && P.xs_ncomp <= XS_STRIDE;
+  P.guard = P.xsums && a->radius_guard != 0 && a->rguard != nullptr && !ipx_cg_resident_ok(a);
   if (box) {
     const int64_t per = (int64_t)IPX_BLOCK * step1_box_rounds(b);
     P.np2 = (int)((b->ng + b->ngen + per - 1) / per);
@@ -1308,22 +1394,23 @@ template <bool PEER> Step1BoxFn<PEER> step1_box_kernel(int group_mode) {
 // k_cg_step1_ar<QS, FT_NNZ, XN, C16, PEER>: 8 forms x QS = 2, 4, 6, 8 (the column span of a row
 // tile in blocks of IPX_BLOCK, rounded up to even; a wider span has no kernel) -- 32.
 //   XN   0: ||x + alpha p||^2 from x and p;  1: not formed (LoopPlan.no_xn2);  2: from the
-//        carried sums, x and p not read
+//        carried sums, x and p not read;  3: the radius guard (LoopPlan.guard), 1 + the bound T
 //   C16  16-bit column offsets (ipx_cg_args.A_col16)
-//   one GPU   XN 0, 1, 2  x  C16 0, 1
+//   one GPU   XN 0, 1, 2, 3  x  C16 0, 1
 //   PEER      XN 0, 1 with C16 only: peer_fusable admits no pattern without the 16-bit tables,
 //             and the carried sums are one GPU's (the ranks' test needs the all-reduced sum)
 template <bool PEER> using Step1ArFn = decltype(&k_cg_step1_ar<2, FT_NNZ, 0, true, PEER>);
 template <bool PEER, int QS> Step1ArFn<PEER> step1_ar_forms(int xn, bool c16) {
   if constexpr (PEER) {
-    static constexpr Step1ArFn<true> K[3] = {k_cg_step1_ar<QS, FT_NNZ, 0, true, true>,
-                                  k_cg_step1_ar<QS, FT_NNZ, 1, true, true>, nullptr};
+    static constexpr Step1ArFn<true> K[4] = {k_cg_step1_ar<QS, FT_NNZ, 0, true, true>,
+                                  k_cg_step1_ar<QS, FT_NNZ, 1, true, true>, nullptr, nullptr};
     return c16 ? K[xn] : nullptr;
   } else {
-    static constexpr Step1ArFn<false> K[3][2] = {
+    static constexpr Step1ArFn<false> K[4][2] = {
         {k_cg_step1_ar<QS, FT_NNZ, 0, false, false>, k_cg_step1_ar<QS, FT_NNZ, 0, true, false>},
         {k_cg_step1_ar<QS, FT_NNZ, 1, false, false>, k_cg_step1_ar<QS, FT_NNZ, 1, true, false>},
-        {k_cg_step1_ar<QS, FT_NNZ, 2, false, false>, k_cg_step1_ar<QS, FT_NNZ, 2, true, false>}};
+        {k_cg_step1_ar<QS, FT_NNZ, 2, false, false>, k_cg_step1_ar<QS, FT_NNZ, 2, true, false>},
+        {k_cg_step1_ar<QS, FT_NNZ, 3, false, false>, k_cg_step1_ar<QS, FT_NNZ, 3, true, false>}};
     return K[xn][c16 ? 1 : 0];
   }
 }
@@ -1337,35 +1424,39 @@ template <bool PEER> Step1ArFn<PEER> step1_ar_kernel(int qs, int xn, bool c16) {
   return nullptr;
 }
 
-// k_cg_step2_hp<HAS_DIAG, Q, QS, BOX, C16, PEER, XSUM>: 8 forms x HAS_DIAG x (Q, QS) -- 32.
+// k_cg_step2_hp<HAS_DIAG, Q, QS, BOX, C16, PEER, XSUM, GUARD>: 10 forms x HAS_DIAG x (Q, QS) -- 40.
 //   (Q, QS)  (3, 3) for short row tiles -- 3 nonzeros per row -> 683 rows: 3 elements per lane,
 //            fewer registers -- else (4, 5)
 //   one GPU  BOX 0, 1  x  C16 0, 1 without XSUM;  XSUM x C16 0, 1 without BOX: the carried sums
-//            need the fused step1, which a box excludes (a box wins: XSUM is not looked at)
+//            need the fused step1, which a box excludes (a box wins: XSUM is not looked at);
+//            GUARD x C16 0, 1 without BOX and XSUM (the radius guard, where XSUM would apply)
 //   PEER     BOX 0, 1 with C16 only (peer_fusable), never XSUM (the carried sums are one GPU's)
 template <bool PEER> using Step2HpFn = decltype(&k_cg_step2_hp<true, 4, 5, false, true, PEER>);
 template <bool PEER, bool D, int Q, int QS>
-Step2HpFn<PEER> step2_hp_forms(bool box, bool c16, bool xsum) {
+Step2HpFn<PEER> step2_hp_forms(bool box, bool c16, bool xsum, bool guard) {
   if constexpr (PEER) {
     if (!c16) return nullptr;
     return box ? k_cg_step2_hp<D, Q, QS, true, true, true>
                : k_cg_step2_hp<D, Q, QS, false, true, true>;
   } else {
-    static constexpr Step2HpFn<false> K[3][2] = {
+    static constexpr Step2HpFn<false> K[4][2] = {
         {k_cg_step2_hp<D, Q, QS, false, false, false>, k_cg_step2_hp<D, Q, QS, false, true, false>},
         {k_cg_step2_hp<D, Q, QS, true, false, false>, k_cg_step2_hp<D, Q, QS, true, true, false>},
         {k_cg_step2_hp<D, Q, QS, false, false, false, true>,
-         k_cg_step2_hp<D, Q, QS, false, true, false, true>}};
-    return K[box ? 1 : xsum ? 2 : 0][c16 ? 1 : 0];
+         k_cg_step2_hp<D, Q, QS, false, true, false, true>},
+        {k_cg_step2_hp<D, Q, QS, false, false, false, false, true>,
+         k_cg_step2_hp<D, Q, QS, false, true, false, false, true>}};
+    return K[box ? 1 : guard ? 3 : xsum ? 2 : 0][c16 ? 1 : 0];
   }
 }
 template <bool PEER>
-Step2HpFn<PEER> step2_hp_kernel(bool diag, bool small, bool box, bool c16, bool xsum) {
+Step2HpFn<PEER> step2_hp_kernel(bool diag, bool small, bool box, bool c16, bool xsum,
+                                bool guard) {
   if (diag)
-    return small ? step2_hp_forms<PEER, true, 3, 3>(box, c16, xsum)
-                 : step2_hp_forms<PEER, true, 4, 5>(box, c16, xsum);
-  return small ? step2_hp_forms<PEER, false, 3, 3>(box, c16, xsum)
-               : step2_hp_forms<PEER, false, 4, 5>(box, c16, xsum);
+    return small ? step2_hp_forms<PEER, true, 3, 3>(box, c16, xsum, guard)
+                 : step2_hp_forms<PEER, true, 4, 5>(box, c16, xsum, guard);
+  return small ? step2_hp_forms<PEER, false, 3, 3>(box, c16, xsum, guard)
+               : step2_hp_forms<PEER, false, 4, 5>(box, c16, xsum, guard);
 }
 
 // ---- single launches --------------------------------------------------------------------
@@ -1386,21 +1477,25 @@ int launch_step1_box(const ipx_cg_args *a, int it, const double *p1, int np1, in
 
 // step1 + A.r in one launch (see k_cg_step1_ar): r_next <- r + alpha Hp, w <- A r_next.
 // no_xn2: x and p are not read, 16 of the kernel's 56 MB at n = 1e6.  carried (a finite radius,
-// no box): the lean form that folds the carried sums' raw partials instead (XN = 2).
+// no box): the lean form that folds the carried sums' raw partials instead (XN = 2).  guard: the
+// radius guard's form (XN = 3), which takes the guard's words where XN = 2 takes the folded sums.
 template <bool PEER>
 int launch_step1_ar(const ipx_cg_args *a, const LoopPlan &P, int it, const double *p1, int np1,
-                    bool no_xn2, bool carried, typename peer_arg<PEER>::type pj, hipStream_t st) {
+                    bool no_xn2, bool carried, bool guard, typename peer_arg<PEER>::type pj,
+                    hipStream_t st) {
   if (carried && (PEER || no_xn2 || !a->xsums)) return IPX_EINVAL;
+  if (guard && (PEER || no_xn2 || carried || !a->rguard)) return IPX_EINVAL;
   if (a->A_tile_nnz != 0) return IPX_EINVAL;    // (the 1024-nonzero tile form was removed)
   const int qs = (int)((a->A_span + IPX_BLOCK - 1) / IPX_BLOCK);
-  const auto k = step1_ar_kernel<PEER>(qs, carried ? 2 : no_xn2 ? 1 : 0, a->A_col16 != nullptr);
+  const auto k = step1_ar_kernel<PEER>(qs, guard ? 3 : carried ? 2 : no_xn2 ? 1 : 0,
+                                       a->A_col16 != nullptr);
   if (!k) return IPX_EINVAL;      // (a wider span; PEER without the 16-bit tables: peer_fusable)
   const int nraw = carried ? (int)a->H_ntiles : 0;
   hipLaunchKernelGGL(k, dim3(ipx_xcd_grid((int)a->A_ntiles)), dim3(IPX_BLOCK), 0, st, (int)a->n,
                      a->state, it & 1, p1, np1, a->x, a->p, a->r, a->r_next, a->Hp, a->A_rowptr,
                      a->A_colidx, a->A_val, a->A_tiles, (int)a->A_ntiles, a->A_own, a->w,
                      a->part2, (const uint16_t *)a->A_col16, pj, carried ? a->xsums : nullptr,
-                     nraw, carried ? a->xsums + 3 * nraw + 1 : nullptr,
+                     nraw, guard ? a->rguard : carried ? a->xsums + 3 * nraw + 1 : nullptr,
                      carried ? P.xs_ncomp : 0, it);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
@@ -1414,12 +1509,15 @@ int launch_step2_hp(const ipx_cg_args *a, int it, int mode, const double *p2, in
                     const double *p3, int np3, const double *p4, int np4,
                     typename peer_arg<PEER>::type pj, const ipx_xsums_job &xs, hipStream_t st,
                     const double *g = nullptr) {
-  const bool xsum = xs.raw != nullptr && (xs.write != 0 || (mode & 4) != 0);
+  const bool guard = (mode & 8) != 0;           // (the radius guard: xs.in = its three words)
+  const bool xsum = !guard && xs.raw != nullptr && (xs.write != 0 || (mode & 4) != 0);
   if ((mode & 4) && (!xsum || !xs.in || PEER || a->lb)) return IPX_EINVAL;
+  if (guard && (!xs.raw || !xs.in || xs.write || (mode & 4) || PEER || a->lb)) return IPX_EINVAL;
   // H_tile_rows: the longest tile's row count (set by the host binding)
   const bool small = a->H_tile_rows > 0 && a->H_tile_rows + 2 * a->H_hmax <= 3 * IPX_BLOCK;
   const bool c16 = a->H_col16 != nullptr && a->H_rowlen != nullptr;
-  const auto k = step2_hp_kernel<PEER>(a->H_diag != nullptr, small, a->lb != nullptr, c16, xsum);
+  const auto k = step2_hp_kernel<PEER>(a->H_diag != nullptr, small, a->lb != nullptr, c16, xsum,
+                                       guard);
   if (!k) return IPX_EINVAL;      // (PEER without the 16-bit tables: see peer_fusable)
   const int64_t half = a->H_ntiles * 2 * a->H_hmax;
   const double *pb_in = a->pb + (it & 1) * half;
@@ -1522,7 +1620,8 @@ struct Compactor {
 struct HalfArgs {
   int it;
   // step2's mode bits: 1 no ||x + alpha p||^2 (LoopPlan.no_xn2), 2 no orthogonality test, 4 the
-  // radius test from the carried sums.  The projection half reads 1 and 4 (for its step1)
+  // radius test from the carried sums, 8 from the radius guard's bound (no sums; xs.in = rguard).
+  // The projection half reads 1, 4 and 8 (for its step1)
   int mode;
   const double *guard;                  // the stop word, for the launches that take one
   const OwnRanges *own = nullptr;       // the rank's own entries (sharded loop); NULL: every entry
@@ -1553,16 +1652,17 @@ int launch_projection_half(const ipx_cg_args *a, const LoopPlan &P, const HalfAr
   }
   if (P.proj == PJ_STEP1_SOLVE_TAIL) {
     if (h.peer || h.own) return IPX_EINVAL;
-    const bool carried = (h.mode & 4) != 0;
+    const bool carried = (h.mode & 4) != 0, guarded = (h.mode & 8) != 0;
     if (carried && ((h.mode & 1) || !a->xsums)) return IPX_EINVAL;
+    if (guarded && ((h.mode & 5) || !a->rguard)) return IPX_EINVAL;
     const int nraw = carried ? (int)a->H_ntiles : 0;
     ipx_fused_proj_job J{};
     J.st = a->state; J.parity = h.it & 1; J.p1 = p1 + np1; J.np1 = np1;
     J.r_in = h.flip ? a->r_next : a->r; J.Hp = a->Hp; J.g_out = h.flip ? a->r : a->r_next;
-    J.xn = carried ? 2 : (h.mode & 1) ? 1 : 0;
+    J.xn = guarded ? 3 : carried ? 2 : (h.mode & 1) ? 1 : 0;
     J.x = a->x; J.p = a->p; J.part2 = a->part2;
     J.xs_raw = carried ? a->xsums : nullptr; J.nraw = nraw;
-    J.xs_comp = carried ? a->xsums + 3 * nraw + 1 : nullptr;
+    J.xs_comp = guarded ? a->rguard : carried ? a->xsums + 3 * nraw + 1 : nullptr;
     J.ncomp = carried ? P.xs_ncomp : 0; J.it = h.it;
     J.A_ell_val = a->A_ell_val; J.A_ell_off16 = (const uint16_t *)a->A_ell_off16;
     J.contig = a->A_contig != 0;
@@ -1583,8 +1683,9 @@ int launch_projection_half(const ipx_cg_args *a, const LoopPlan &P, const HalfAr
   switch (P.step1) {
     case S1_FUSED_AR:
       MARK(1);
-      rc = h.peer ? launch_step1_ar<true>(a, P, h.it, p1, np1, h.mode & 1, h.mode & 4, *h.peer, st)
-                  : launch_step1_ar<false>(a, P, h.it, p1, np1, h.mode & 1, h.mode & 4,
+      rc = h.peer ? launch_step1_ar<true>(a, P, h.it, p1, np1, h.mode & 1, h.mode & 4, h.mode & 8,
+                                          *h.peer, st)
+                  : launch_step1_ar<false>(a, P, h.it, p1, np1, h.mode & 1, h.mode & 4, h.mode & 8,
                                            ipx_no_peer{}, st);
       if (rc) return rc;
       MARK(2);
@@ -1701,7 +1802,8 @@ int launch_update_half(const ipx_cg_args *a, const LoopPlan &P, const HalfArgs &
   if (h.cmp) {
     // every workgroup folds all of them: at n = 1.6e7 the 6000 uncompacted ||g||^2 partials
     // doubled what a workgroup of the fused kernel reads (495 us on its own, 226 us in the loop)
-    if (!(h.mode & 5)) h.cmp->add(p2, np2, 2, 1024);       // (bit 4: the folded sums in its place)
+    // (bit 4: the folded sums in its place; bit 8: the guard's bound, nothing folded)
+    if (!(h.mode & 13)) h.cmp->add(p2, np2, 2, 1024);
     h.cmp->add(p3, np3, 2, 2048);
     if (!(h.mode & 2)) h.cmp->add(p4, np4, 1, 1024);
     rc = h.cmp->launch(st);
@@ -1758,14 +1860,18 @@ int cg_iterate(const ipx_cg_args *a, const LoopPlan &P, int32_t it_begin, int32_
     // H.p kernel left (ipx_cg_args.xsums) -- inside a batch, or where the caller vouches for
     // the batch before; the fused step1 then reads neither x nor p.  The first iteration of a
     // call reads them as before.
-    const bool carried = P.xsums && (it > it_begin || a->xsums_carry != 0);
+    // Under the radius guard neither form runs: the test is decided from the bound T the
+    // projection half leaves (mode bit 8), no sums are written and their tag is cleared.
+    const bool carried = P.xsums && !P.guard && (it > it_begin || a->xsums_carry != 0);
     Compactor cmp(a, guard);
-    HalfArgs h{it, (P.proj == PJ_NONE ? 2 : 0) | (P.no_xn2 ? 1 : 0) | (carried ? 4 : 0), guard};
+    HalfArgs h{it, (P.proj == PJ_NONE ? 2 : 0) | (P.no_xn2 ? 1 : 0) | (carried ? 4 : 0) |
+                       (P.guard ? 8 : 0), guard};
     if (P.proj != PJ_DENSE) h.cmp = &cmp;            // (the dense loop never compacted)
     // the fused step2 + H.p writes the sums (or voids their tag) and, carried, reads the sums
     // the fused step1 folded (in part2's place)
-    h.xs = ipx_xsums_job{a->xsums, carried ? a->xsums + 3 * a->H_ntiles + 1 : nullptr, it,
-                         P.xsums ? 1 : 0};
+    h.xs = ipx_xsums_job{a->xsums,
+                         P.guard ? a->rguard : carried ? a->xsums + 3 * a->H_ntiles + 1 : nullptr,
+                         it, P.xsums && !P.guard ? 1 : 0};
     h.ev = ev;
     h.first = it == it_begin;
     h.flip = P.proj == PJ_STEP1_SOLVE_TAIL && ((it - it_begin) & 1) != 0;
@@ -2112,9 +2218,12 @@ int ipx_cg_shard2_fold_hp(const ipx_cg_args *a, const ipx_shard2_ext *e, void *s
 // taken (may be NULL): taken[pj] != 0 when projection pj already had its one correction step on
 // the device (ipx_cg_prime: k_prime_decide) -- like the host's loop after its first step
 // (projector.null_space, k >= 1) only the orthogonality test then stands.
+// rguard (may be NULL): the radius guard's words X, Q, T (ipx_cg_args.rguard) -- X0 >= ||x0||
+// from the reduction slot of ||x0||^2 (0 without one), Q0 >= ||p0|| = ||g0|| from rt_g, T = 0.
 __device__ void prime_state_body(double *st, const double *red, const ipx_prime_idx &ix,
                                  double tol_in, double radius, double orth_tol, double norm_A,
-                                 double canc2, const double *taken = nullptr) {
+                                 double canc2, const double *taken = nullptr,
+                                 double *rguard = nullptr) {
   double q[7];
   for (int k = 0; k < 7; ++k) q[k] = ix.i[k] >= 0 ? red[ix.i[k]] : 0.0;
   bool bad = false;
@@ -2140,13 +2249,18 @@ __device__ void prime_state_body(double *st, const double *red, const ipx_prime_
   st[ST_MARGIN] = margin;
   st[ST_PRIME_STEPS] = taken ? taken[0] + taken[1] : 0.0;
   st[ST_STOP] = bad ? 9.0 : 0.0;
+  if (rguard) {
+    rguard[IPX_RG_X] = ipx_rguard::start(q[0]);
+    rguard[IPX_RG_Q] = ipx_rguard::start(rt_g);
+    rguard[IPX_RG_T] = 0.0;
+  }
 }
 
 __global__ void k_cg_prime_state(double *st, const double *__restrict__ red, ipx_prime_idx ix,
                                  double tol_in, double radius, double orth_tol, double norm_A,
-                                 double canc2) {
+                                 double canc2, double *rguard) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  prime_state_body(st, red, ix, tol_in, radius, orth_tol, norm_A, canc2);
+  prime_state_body(st, red, ix, tol_in, radius, orth_tol, norm_A, canc2, nullptr, rguard);
 }
 
 // The same behind the folds of the priming's SpMV partials (ipx_cg_prime: up to six products
@@ -2217,7 +2331,8 @@ __global__ void __launch_bounds__(IPX_BLOCK)
 k_cg_prime_state_folds(double *st, double *red, PrimeFolds f, ipx_prime_idx ix, double tol_in,
                        double radius, double orth_tol, double norm_A, double canc2,
                        const double *__restrict__ radius_dev,
-                       const double *__restrict__ norm_A2_dev, PrimeStep last, int have_last) {
+                       const double *__restrict__ norm_A2_dev, PrimeStep last, int have_last,
+                       double *rguard) {
   if (radius_dev) radius = *radius_dev;
   if (norm_A2_dev) norm_A = sqrt(*norm_A2_dev);
   // all twelve sums (six jobs x [sum y^2 | sum x y]) in one pass: the loads of every array in
@@ -2248,19 +2363,26 @@ k_cg_prime_state_folds(double *st, double *red, PrimeFolds f, ipx_prime_idx ix, 
   // (thread 0 reads back what it wrote itself)
   if (threadIdx.x == 0)
     prime_state_body(st, red, ix, tol_in, radius, orth_tol, norm_A, canc2,
-                     have_last ? red + PR_TAKEN : nullptr);
+                     have_last ? red + PR_TAKEN : nullptr, rguard);
+}
+
+int ipx_cg_prime_state_guard(double *state, const double *red, const int32_t *idx7,
+                             double tol_in, double radius, double orth_tol, double norm_A,
+                             double cancellation, double *rguard, void *stream) {
+  if (!state || !red || !idx7) return IPX_EINVAL;
+  ipx_prime_idx ix;
+  for (int k = 0; k < 7; ++k) ix.i[k] = idx7[k];
+  hipLaunchKernelGGL(k_cg_prime_state, dim3(1), dim3(64), 0, (hipStream_t)stream, state, red, ix,
+                     tol_in, radius, orth_tol, norm_A, cancellation * cancellation, rguard);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
 }
 
 int ipx_cg_prime_state(double *state, const double *red, const int32_t *idx7, double tol_in,
                        double radius, double orth_tol, double norm_A, double cancellation,
                        void *stream) {
-  if (!state || !red || !idx7) return IPX_EINVAL;
-  ipx_prime_idx ix;
-  for (int k = 0; k < 7; ++k) ix.i[k] = idx7[k];
-  hipLaunchKernelGGL(k_cg_prime_state, dim3(1), dim3(64), 0, (hipStream_t)stream, state, red, ix,
-                     tol_in, radius, orth_tol, norm_A, cancellation * cancellation);
-  IPX_CHECK_LAUNCH();
-  return IPX_OK;
+  return ipx_cg_prime_state_guard(state, red, idx7, tol_in, radius, orth_tol, norm_A, cancellation,
+                                  nullptr, stream);
 }
 
 // The whole priming of a projected_cg call (qp_subproblem.py:502-512) behind ONE entry point:
@@ -2512,7 +2634,7 @@ int ipx_cg_prime_dev(const ipx_cg_args *a, const int32_t *A_tiles, int32_t A_nti
   for (int k = 0; k < 7; ++k) ix.i[k] = (b ? idx_b : idx_0)[k];
   hipLaunchKernelGGL(k_cg_prime_state_folds, dim3(1), dim3(IPX_BLOCK), 0, st, a->state, red, R.f,
                      ix, tol_in, radius, orth_tol, norm_A, canc2, radius_dev, norm_A2_dev, s2,
-                     (b || !steps) ? 0 : 1);
+                     (b || !steps) ? 0 : 1, a->radius_guard != 0 ? a->rguard : nullptr);
   IPX_CHECK_LAUNCH();
   rc = launch_hp(a, P, nullptr, st);
   if (rc || first_end == 0) return rc;
@@ -2551,8 +2673,50 @@ int ipx_cg_resume(const ipx_cg_args *a, int32_t it, int32_t mode, void *stream) 
   LoopPlan P = plan_of(a);
   P.step2 = S2_VECTOR;
   const HalfArgs h{it, mode, a->state + ST_STOP};
-  return launch_update_half(a, P, h, a->part2, P.np2, a->part3, P.np3, a->part4, P.np4,
-                            (hipStream_t)stream);
+  // the radius guard: the vector step2 moves x and p without the guard's kernel -- only behind a
+  // test that was taken (mode bit 1: part2 holds nothing), and the bounds move with them
+  if (P.guard && !(mode & 1)) return IPX_EINVAL;
+  int rc = launch_update_half(a, P, h, a->part2, P.np2, a->part3, P.np3, a->part4, P.np4,
+                              (hipStream_t)stream);
+  if (rc || !P.guard) return rc;
+  // (the H.p launches behind step2 leave the state block alone)
+  hipLaunchKernelGGL(k_rguard_advance, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                     (const double *)a->state, it & 1, a->rguard);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+// The radius guard lost on iteration it_stop (stop code 11, cleared by the caller): the sums the
+// carried form would hold, then that iteration's update half in the carried form.
+int ipx_cg_guard_resume(const ipx_cg_args *a, int32_t it_stop, void *stream) {
+  if (!a || !a->xsums || !a->rguard) return IPX_EINVAL;
+  LoopPlan P = plan_of(a);
+  if (!P.xsums || P.step2 != S2_FUSED_HP) return IPX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  double *comp = a->xsums + 3 * a->H_ntiles + 1;
+  hipLaunchKernelGGL(k_rguard_sums, dim3(XS_STRIDE), dim3(IPX_BLOCK), 0, st, a->n,
+                     (const double *)a->x, (const double *)a->p, comp);
+  IPX_CHECK_LAUNCH();
+  const double *guard = a->state + ST_STOP;
+  Compactor cmp(a, guard);
+  HalfArgs h{it_stop, 4, guard};
+  h.cmp = &cmp;
+  h.xs = ipx_xsums_job{a->xsums, comp, it_stop, 1};
+  int rc = launch_update_half(a, P, h, a->part2, P.np2, a->part3, P.np3, a->part4, P.np4, st);
+  if (rc) return rc;
+  // the folded arrays as the loop's launches expect them: zeros behind the xs_ncomp entries the
+  // projection half of the next carried iteration writes
+  if (hipMemsetAsync(comp, 0, (size_t)3 * XS_STRIDE * sizeof(double), st) != hipSuccess)
+    return IPX_ELAUNCH;
+  return IPX_OK;
+}
+
+double ipx_rguard_start(double sumsq) { return ipx_rguard::start(sumsq); }
+double ipx_rguard_step_x(double X, double Q, double alpha) {
+  return ipx_rguard::step_x(X, Q, alpha);
+}
+double ipx_rguard_step_q(double Q, double beta, double gg) {
+  return ipx_rguard::step_q(Q, beta, gg);
 }
 
 int ipx_cg_iterate(const ipx_cg_args *a, int32_t it_begin, int32_t it_end, void *stream) {

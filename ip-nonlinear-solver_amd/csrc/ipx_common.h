@@ -712,6 +712,24 @@ int ipx_banded_solve_resid_launch(void *handle, const double *w, double *x, doub
 // on the workgroup's own variables.  What the kernel reads beside the factorization:
 constexpr int IPX_XS_SLICE = 64;            // raw partials per folded carried sum (one wave)
 constexpr int IPX_XS_STRIDE = IPX_BLOCK;    // distance of the three arrays of folded sums
+// The radius guard (ipx_cg_args.rguard = X, Q, T): one step of the norm bounds, for the lead
+// lanes of the loop's kernels and for the host (ipx_rguard_step_x / _q / _start export it).
+// X >= ||x||, Q >= ||p|| give ||x + alpha p|| <= X + |alpha| Q and ||beta p - g|| <= beta Q +
+// ||g|| (beta = gg / rtg >= 0).  Every update is inflated by 1 + 2^-20: the worst-case error of a
+// sum of n <= 2^31 squares in any order is <= 2^-22 relative (gg, ||x0||^2), the roundings of
+// fl(x + fl(alpha p)) and fl(fl(beta p) - g) and of these few operations are <= 2^-50 -- a
+// factor of about 4 in hand; compounded, 1 % of looseness after 1e4 iterations.
+constexpr int IPX_RG_X = 0, IPX_RG_Q = 1, IPX_RG_T = 2;
+struct ipx_rguard {
+  static constexpr double INFL = 1.0 + 0x1p-20;
+  static __host__ __device__ inline double start(double sumsq) { return sqrt(sumsq) * INFL; }
+  static __host__ __device__ inline double step_x(double X, double Q, double alpha) {
+    return (X + fabs(alpha) * Q) * INFL;
+  }
+  static __host__ __device__ inline double step_q(double Q, double beta, double gg) {
+    return (beta * Q + sqrt(gg)) * INFL;
+  }
+};
 constexpr int IPX_FP_SPAN = 4096;           // span columns per workgroup (LDS)
 constexpr int IPX_FP_ROW = 16;              // entries per row of A (registers)
 struct ipx_fused_proj_job {
@@ -739,6 +757,9 @@ struct ipx_fused_proj_job {
   // prime != 0: the projection alone (the priming): st, p1, Hp, where unused; xn = 1;
   // g = sign (r_in - A'v); *guard != 0 (or NULL: never) skips the launch
   int prime; double sign; const double *guard;
+  // xn = 3 (the radius guard): as xn = 1, and the lead lane stores T = (X + |alpha| Q)(1 + 2^-20)
+  // into xs_comp[2] -- xs_comp then points at ipx_cg_args.rguard (X, Q, T), the struct has no
+  // field of its own for it (its size is part of every instantiation's argument segment)
 };
 // IPX_EUNSUPPORTED when the factorization, the window or the tables do not fit the kernel
 int ipx_banded_fused_proj_ok(void *handle, int rl, int64_t nspan, int qv);

@@ -72,6 +72,8 @@ _SIGNATURES = {
     "ipx_cg_vec_grid": [_I64],
     "ipx_cg_hp": [_P, _P],
     "ipx_cg_resume": [_P, _I32, _I32, _P],
+    "ipx_cg_guard_resume": [_P, _I32, _P],
+    "ipx_cg_prime_state_guard": [_P, _P, _P, _F64, _F64, _F64, _F64, _F64, _P, _P],
     "ipx_cg_iterate": [_P, _I32, _I32, _P],
     "ipx_cg_resident_ok": [_P],
     "ipx_cg_prime_state": [_P, _P, _P, _F64, _F64, _F64, _F64, _F64, _P],
@@ -195,8 +197,11 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_blockwide_ws_doubles": _I64, "ipx_nd_symbolic": _I64,
              "ipx_qr_padded_cols": _I64, "ipx_qr_ws_doubles": _I64,
              "ipx_qrp_ws_doubles": _I64, "ipx_qrp_info_doubles": _I64,
-             "ipx_qrp_info_ints": _I64}
+             "ipx_qrp_info_ints": _I64,
+             "ipx_rguard_start": _F64, "ipx_rguard_step_x": _F64, "ipx_rguard_step_q": _F64}
 _EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
+                   "ipx_rguard_start": [_F64], "ipx_rguard_step_x": [_F64, _F64, _F64],
+                   "ipx_rguard_step_q": [_F64, _F64, _F64],
                    "ipx_qr_padded_cols": [_I64], "ipx_qr_ws_doubles": [_I64, _I64],
                    "ipx_qrp_ws_doubles": [_I64, _I64], "ipx_qrp_info_doubles": [_I64],
                    "ipx_qrp_info_ints": [_I64],
@@ -286,11 +291,14 @@ def load():
 #   no-fused-projection  problems beyond the resident kernel's size: step1 + A.r, the solve with
 #                      its tail and step2 + H.p as three launches per iteration instead of the
 #                      projection half as one (csrc/banded.hip k_step1_solve_tail)
+#   no-radius-guard    finite trust radius: the test of :583 from the carried sums (or x and p)
+#                      in every iteration, never from the norm bound (ipx_cg_args.radius_guard
+#                      stays 0)
 #   table-columns      the fused projection reads the 16-bit column offsets of A even where every
 #                      row is a run of consecutive columns (ipx_cg_args.A_contig stays 0)
 DEBUG_FORMS = ("no-fuse", "no-resident", "no-compact-groups", "no-affine-groups", "keep-xn2",
                "read-xn2", "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop",
-               "no-fused-projection", "table-columns")
+               "no-fused-projection", "table-columns", "no-radius-guard")
 
 
 def debug_form(name):

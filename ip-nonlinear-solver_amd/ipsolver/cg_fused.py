@@ -49,7 +49,8 @@ class CgArgs(ctypes.Structure):
         ("LR_W", _P), ("LR_state", _P), ("LR_part", _P), ("LR_mem", _I64), ("LR_rows", _I64),
         ("xsums", _P),
         ("fused_proj", _I64), ("A_ell_val", _P), ("A_ell_off16", _P), ("r_where", _P),
-        ("xsums_carry", ctypes.c_int32), ("A_contig", ctypes.c_int32))]
+        ("xsums_carry", ctypes.c_int32), ("A_contig", ctypes.c_int32),
+        ("rguard", _P), ("radius_guard", ctypes.c_int32))]
 
 
 # Counters over the life of the process (diagnostics: how often the device loop
@@ -61,7 +62,8 @@ STATS = {"calls": 0, "iterations": 0, "batches": 0, "box_events": 0, "refine_eve
          "resident_calls": 0,     # solves whose batches ran as resident launches (csrc/resident.hip)
          "resident_fallbacks": 0, # batches repeated on the separate launches (stop code 8)
          "operator_calls": 0,     # solves whose Hessian was an operator applied by the host
-         "radius_undecided": 0}   # radius tests the carried sums left to the host (stop code 10)
+         "radius_undecided": 0,   # radius tests the carried sums left to the host (stop code 10)
+         "guard_lost": 0}         # calls whose radius guard gave way to the carried sums (code 11)
 
 
 def _hessian_parts(H):
@@ -524,7 +526,9 @@ def _loop_for(H, P, lb, ub):
 
 def _release(L, key):
     """Park the loop object for the next call on the same patterns; the iterate it returned
-    stays the caller's (a fresh buffer takes its place)."""
+    stays the caller's (a fresh buffer takes its place).  The radius guard is a call's: a
+    parked argument block always describes the exact form."""
+    L.args.radius_guard = 0
     if key is None:
         return
     if len(_POOL) >= 4:
@@ -575,8 +579,11 @@ class _Loop:
         a.fused_proj = 0
         a.no_radius = 0
         a.xsums_carry = 0
+        a.radius_guard = 0
         if self.xsums is not None:
             self.xsums.zero_()          # (no tag survives into another call's x and p)
+        if self.rguard is not None:
+            self.rguard.zero_()         # (nor a bound on them)
         self.x = torch.empty(self.n, dtype=torch.float64, device=self.state.device)
         a.x = _ptr(self.x)
         self.keep = (A, At, Hc, Hd, lb, ub, P, LR)
@@ -607,6 +614,21 @@ class _Loop:
         a.fused_proj = 1
         return True
 
+    def arm_radius_guard(self, key, trust_radius, has_box):
+        """Switch the radius guard (ipx_cg_args.radius_guard) on for this call where it
+        applies: a finite radius, no box, the carried sums' buffers bound and no resident
+        launch -- and not on patterns whose last call lost the guard (``_GUARD_LOST``: such a
+        call pays a pass over x and p on top of the carried form; it starts exact until a call
+        ends inside the trust region).  True when it is on."""
+        a = self.args
+        a.radius_guard = 0
+        if self.rguard is None or self.xsums is None or has_box or a.no_radius \
+                or not np.isfinite(trust_radius) or a.resident \
+                or _hip.debug_form("no-radius-guard") or (key is not None and key in _GUARD_LOST):
+            return False
+        a.radius_guard = 1
+        return True
+
     def _bind_lowrank(self, LR):
         """ipx_cg_args.LR_*: the low-rank term's buffers (its memory: the same for a whole solve)"""
         a = self.args
@@ -630,6 +652,7 @@ class _Loop:
         from .dense import DeviceDense
         self.geometry, self.pcr_L, self.operator = None, None, None
         self.xsums = None
+        self.rguard = None
         self.fp_tabs = None          # window tables of the fused projection, when bound
         if isinstance(P.A, DeviceDense):
             self._init_dense(H, P, lb, ub)
@@ -723,6 +746,11 @@ class _Loop:
                 nt = Hc.pattern.ntiles
                 self.xsums = torch.zeros(3 * nt + 1 + 3 * 256 + 1, dtype=f64, device=dev)
                 a.xsums = _ptr(self.xsums)
+                # ... or, while a bound on ||x + alpha p|| stays below the radius, from that
+                # bound alone (the radius guard, ipx_cg_args.rguard = X, Q, T: armed per call,
+                # arm_radius_guard)
+                self.rguard = torch.zeros(3, dtype=f64, device=dev)
+                a.rguard = _ptr(self.rguard)
         # tridiagonal A A' on the single-launch solve: g = r - A'v rides in that launch
         if a.solver_kind == 0 and not no_fuse:
             geo = (ctypes.c_int32 * 2)()
@@ -865,6 +893,7 @@ class _ResidentGaveUp(Exception):
 
 _NO_RESIDENT = set()       # pool signatures whose resident launches timed out once
 _INJECT_RESIDENT_TIMEOUT = []      # tests append one item: the next resident batch "times out"
+_WATCH_BATCHES = []        # tests append callables: f(loop object, (it, end)) behind every state read
 
 
 def projected_cg(H, c, Z, Y, b, trust_radius=np.inf, lb=None, ub=None, tol=None,
@@ -932,6 +961,7 @@ def _projected_cg_once(H, c, Z, Y, b, trust_radius, lb, ub, tol, max_iter, max_i
 
 
 _HOST_PRIMED = set()       # pool signatures whose last call needed the host's priming
+_GUARD_LOST = set()        # ... whose last call with a finite radius lost the radius guard
 _STEP_PRIMED = set()       # ... whose primings carry the projections' correction steps (device)
 
 
@@ -954,10 +984,11 @@ def _prime_without_reads(L, H, c, Z, Y, b, b_zero, P, tol, trust_radius):
         t = H.dot(x0) + c
     r0 = P.null_space_enqueue(t, 0)          # ||t||^2 -> 4, ||r0||^2 -> 0, ||A r0||^2 -> 2
     g0 = P.null_space_enqueue(r0, 6)         # ||r0||^2 -> 10, ||g0||^2 -> 6, ||A g0||^2 -> 8
-    _hip.call("ipx_cg_prime_state", _p(L.state), _p(ctx_.out),
+    _hip.call("ipx_cg_prime_state_guard", _p(L.state), _p(ctx_.out),
               _PRIME_IDX_B0 if b_zero else _PRIME_IDX,
               float("nan") if tol is None else float(tol), float(trust_radius),
-              float(P.orth_tol), float(P.norm_A), float(P.CANCELLATION), stream_ptr())
+              float(P.orth_tol), float(P.norm_A), float(P.CANCELLATION),
+              _p(L.rguard) if L.args.radius_guard else None, stream_ptr())
     return x0, r0, g0
 
 
@@ -986,6 +1017,7 @@ def _projected_cg(H, c, Z, Y, b, trust_radius, lb, ub, tol, max_iter, max_infeas
         if np.isinf(trust_radius) and trust_radius > 0 and not has_box \
                 and not _hip.debug_form("keep-xn2"):
             L.args.no_radius = 1
+        L.arm_radius_guard(pool_key, trust_radius, has_box)
         st = stream_ptr()
         a = L.args
         if isinstance(P.A, DeviceCSR) and a.solver_kind in (0, 1) and getattr(P.solver, "perm", None) is None \
@@ -1052,6 +1084,11 @@ def _projected_cg(H, c, Z, Y, b, trust_radius, lb, ub, tol, max_iter, max_infeas
     if np.isinf(trust_radius) and trust_radius > 0 and not has_box \
             and not _hip.debug_form("keep-xn2"):
         L.args.no_radius = 1
+    if L.arm_radius_guard(pool_key, trust_radius, has_box):
+        # X0 >= ||x0||, Q0 >= ||p0|| = ||g0|| as the device priming writes them
+        nx0 = dv.norm(x0) if norm_x0 is None else norm_x0
+        L.rguard.copy_(torch.tensor([nx0 * lib.ipx_rguard_start(1.0), lib.ipx_rguard_start(rt_g),
+                                     0.0], dtype=torch.float64))
     L.arm_fused_projection(min(max_iter, batch if batch
                                 else _first_batch(max_iter, L.operator is not None)))
     st = stream_ptr()
@@ -1137,6 +1174,8 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
             self.settled = int(s[ST_STOP]) == 0
             if mine and int(s[ST_STOP]) == 0 and not L.args.resident and L.xsums is not None:
                 self.carry_at = self.last[1]
+            for watch in _WATCH_BATCHES:
+                watch(L, self.last)
             if fast and int(s[ST_STOP]) == 9:
                 # the device's verdict on the priming: the host must do it (nothing of the
                 # call's inputs was overwritten; the loop's launches were no-ops)
@@ -1196,8 +1235,33 @@ def _run_loop(L, pool_key, P, lib, st, n, lb, ub, trust_radius, max_iter, max_in
             self.carry_at = None
             _refine(P, L, DVec(L.g_tensor(it_stop)))
 
+        guard_lost = False
+
+        def guard_resume(self, it_stop):
+            """Stop code 11: the rest of the call runs the carried-sum form -- iteration
+            ``it_stop`` finished from sums over the current x and p, the next batch on the sums
+            it leaves."""
+            self.guard_lost = True
+            L.args.radius_guard = 0
+            L.state[ST_STOP] = 0.0
+            _hip.check(lib.ipx_cg_guard_resume(L.ref(), it_stop, st), "ipx_cg_guard_resume")
+            s = dv.read_doubles(L.state, L.state.numel())
+            self.settled = int(s[ST_STOP]) == 0
+            self.carry_at = it_stop + 1 if self.settled else None
+            return s
+
+    D = Driver()
     x, niter, stop_cond, hits_boundary = run_device_loop(
-        Driver(), STATS, lb, ub, trust_radius, max_iter, max_infeasible_iter, batch, stats)
+        D, STATS, lb, ub, trust_radius, max_iter, max_infeasible_iter, batch, stats)
+    if pool_key is not None:
+        # a pattern whose call lost the radius guard starts its next calls exact, until one of
+        # them ends inside the trust region
+        if D.guard_lost:
+            if len(_GUARD_LOST) >= 16:
+                _GUARD_LOST.clear()
+            _GUARD_LOST.add(pool_key)
+        elif not hits_boundary:
+            _GUARD_LOST.discard(pool_key)
     STATS["calls"] += 1
     STATS["iterations"] += niter
     STATS["resident_calls"] += 1 if L.args.resident else 0
@@ -1238,6 +1302,15 @@ def run_device_loop(D, counters, lb, ub, trust_radius, max_iter, max_infeasible_
                 nbatch = min(2 * nbatch, D.batch_cap)
             continue
         it_stop = int(s[ST_IT_DONE])     # index of the iteration that raised the flag
+        if stop == 11:
+            # the radius guard's bound reached the radius: the iteration is finished in the
+            # carried-sum form, whose verdict (none, or one of the stops below) stands
+            counters["guard_lost"] = counters.get("guard_lost", 0) + 1
+            s = D.guard_resume(it_stop)
+            stop = int(s[ST_STOP])
+            if stop == 0:
+                it = it_stop + 1
+                continue
         alpha = s[ST_ALPHA]
         if stop == 4:                     # :551
             stop_cond = 4
