@@ -1235,6 +1235,37 @@ int ipx_nd_solve(const ipx_nd_args *a, int32_t nlevels, const int64_t *levels_ho
 int ipx_chol_factor_steps(int64_t M, double *G, int64_t steps, int *flag, double *work,
                           void *stream);
 
+/* ---- the same factorization in SKIP mode, for a rank-deficient A (ipsolver/nested.py
+ * PivotSkippingNestedSolver, ipsolver/sparse_deficient.py).  A pivot d with
+ * |d| <= 2^-43 S_kk (S_kk the assembled diagonal entry, the quantity bit 0 compares with; a zero
+ * row, S_kk = 0, included) is SKIPPED: row perm[k] of A depends on the rows eliminated before it.
+ * Its column of L is zero, its diagonal is stored as +inf, the trailing matrix takes no update, no
+ * flag bit is raised and work[M] does not see it.  A pivot d < -2^-43 S_kk, or a NaN, stays bits
+ * 0 | 2.  What remains is the factorization of A_S A_S', S the kept rows; ipx_nd_solve on it
+ * (unchanged: x / inf = 0) returns (A_S A_S')^-1 w_S on S and exactly 0 on the dropped rows.
+ * Arguments, launch shapes and every other convention as the entries without _skip, whose results
+ * do not change. */
+int ipx_nd_factor_small_skip(const ipx_nd_args *a, int64_t off, int64_t cnt, int32_t fmax,
+                             int32_t assemble_only, void *stream);
+int ipx_nd_factor_large_skip(const ipx_nd_args *a, const int64_t *sn_host,
+                             const int32_t *lists_host, int64_t off, int64_t cnt,
+                             int32_t assemble_only, void *stream);
+int ipx_chol_factor_steps_skip(int64_t M, double *G, int64_t steps, int *flag, double *work,
+                               void *stream);
+/* mark[row] = 1 where the stored diagonal of the row's own position is +inf, else 0 (m ints, the
+ * caller's row order): one pass over the fronts' diagonals */
+int ipx_nd_skipped(const ipx_nd_args *a, int32_t *mark, void *stream);
+/* The q dropped rows d_rows (ascending, 0 <= q <= ipx_border_pmax()) beside the q x q Woodbury
+ * kernels above; Y column-major m x q with zero rows at the dropped rows.
+ * ipx_nd_dropped_fold: t[i] = 0 for a dropped row, else b[i] + sum_j Y[i + m j] b[d_rows[j]]
+ * (j ascending).  ipx_nd_dropped_fill (q >= 1): out[i] = u[i] for a kept row,
+ * out[d_rows[j]] = sum_g part[g * q + j] over the ipx_border_groups(m) partial blocks of an
+ * ipx_border_tdot, g ascending.  One launch each, no atomics. */
+int ipx_nd_dropped_fold(int64_t m, int32_t q, const double *Y, const int32_t *d_rows,
+                        const int32_t *mark, const double *b, double *t, void *stream);
+int ipx_nd_dropped_fill(int64_t m, int32_t q, const double *part, const int32_t *d_rows,
+                        const int32_t *mark, const double *u, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

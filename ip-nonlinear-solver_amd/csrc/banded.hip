@@ -851,7 +851,9 @@ k_down0(LevDev lv, const double *w, double *y, double *__restrict__ gL,
   auto f_E = [=](int i) {
     const int tl = i / (K * K), r = i - tl * K * K, j = r / K, a = r - j * K;
     const int t = min(t0 + tl, P - 1);
-    return t > 0 ? coupE<K>(Bg, m, t * q, j, a) : 0.0;
+    // (j < the chunk's rows: a last chunk shorter than K has no row t q + j, and on the last
+    // diagonal that entry lies past the end of the band storage; chunk_rhs_halves reads j < ct)
+    return (t > 0 && j < chunk_rows(m, q, c, P, t)) ? coupE<K>(Bg, m, t * q, j, a) : 0.0;
   };
   auto f_F = [=](int i) {
     const int tl = i / (K * K), r = i - tl * K * K, jj = r / K, a = r - jj * K;
@@ -1214,7 +1216,8 @@ k_solve_decoupled(LevDev lv, const double *__restrict__ w, double *__restrict__ 
   auto f_E = [=](int i) {
     const int l = i / (K * K), r = i - l * K * K, j = r / K, a = r - j * K;
     const int t = tfirst + l;
-    return (t > 0 && t < P) ? coupE<K>(Bg, m, t * q, j, a) : 0.0;
+    // (j < the chunk's rows: as in k_down0 -- a last chunk shorter than K)
+    return (t > 0 && t < P && j < chunk_rows(m, q, c, P, t)) ? coupE<K>(Bg, m, t * q, j, a) : 0.0;
   };
   auto f_F = [=](int i) {
     const int l = i / (K * K), r = i - l * K * K, jj = r / K, a = r - jj * K;

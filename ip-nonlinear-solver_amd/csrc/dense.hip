@@ -320,6 +320,13 @@ __device__ __forceinline__ double potrf_rsqrt(double d) {
 // Three barriers per block, twelve per tile (the first version took one per COLUMN and formed
 // every column's entries in all 256 threads: 30 us per tile, the largest item of the
 // Cholesky's 2.0 ms at M = 2048).  The strict upper triangle of the tile is zeroed.
+//
+// SKIP (the pivot-skipping factorization of csrc/nested.hip; the dense path never sets it): a
+// pivot with |d| <= IPX_PIVOT_RTOL x its diagonal entry is not an event but a dropped row --
+// its column of L is zero (rs = 0: l = 0 in every lane of (a), xj = 0 in (b), and k_trsm64
+// forms rinv = 1 / inf = 0), its diagonal is stored as +inf, it raises no bit and work[M] does
+// not see it.  A pivot below -IPX_PIVOT_RTOL x the entry, or a NaN, is bits 0 | 2 as without.
+template <bool SKIP>
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_potrf64(double *G, int M, int kb, int *flag, double *work) {
   __shared__ double T[FB][FB + 1];
@@ -355,7 +362,8 @@ k_potrf64(double *G, int M, int kb, int *flag, double *work) {
 #pragma unroll
       for (int j = 0; j < PB; ++j) {
         const double d = lane_bcast(x[j], j);
-        if (tid == 0) {
+        const bool skip = SKIP && fabs(d) <= IPX_PIVOT_RTOL * diag0[c0 + j];
+        if (tid == 0 && !skip) {
           // bit 1: the pivot lost 43 bits against its diagonal entry (numerically rank deficient,
           // the factorization goes on); bit 4: it is not positive (no factorization)
           const double d0 = diag0[c0 + j];
@@ -363,9 +371,9 @@ k_potrf64(double *G, int M, int kb, int *flag, double *work) {
           if (d > 0.0) ratio = fmin(ratio, d / d0);
         }
         const double dd = d > 0.0 ? d : 1.0;
-        const double rs = potrf_rsqrt(dd);
-        const double l = x[j] * rs;                   // (lane j: d / sqrt(d) = L[j][j] to an ulp)
-        x[j] = l;
+        const double rs = skip ? 0.0 : potrf_rsqrt(dd);
+        const double l = skip ? 0.0 : x[j] * rs;      // (lane j: d / sqrt(d) = L[j][j] to an ulp)
+        x[j] = (skip && tid == j) ? __builtin_huge_val() : l;
         if (tid == j) rinv[c0 + j] = rs;
 #pragma unroll
         for (int c = j + 1; c < PB; ++c) x[c] = __builtin_fma(-l, lane_bcast(l, c), x[c]);
@@ -618,6 +626,27 @@ k_dense_gemvt(int m, int n, const double *__restrict__ B, int64_t ldb,
   if (g == 0 && k < n) y[k] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
 }
 
+// `steps` tile-column steps with the given diagonal-tile kernel (k_potrf64<false> or <true>)
+int chol_factor_steps(void (*potrf)(double *, int, int, int *, double *), int64_t M, double *G,
+                      int64_t steps, int *flag, double *work, void *stream) {
+  if (M < FB || M % FB || steps < 0 || steps > M / FB || !G || !flag || !work) return IPX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = (int)(M / FB);
+  for (int k = 0; k < (int)steps; ++k) {
+    hipLaunchKernelGGL(potrf, dim3(1), dim3(IPX_BLOCK), 0, st, G, (int)M, k, flag, work);
+    IPX_CHECK_LAUNCH();
+    const int rest = nb - k - 1;
+    if (rest > 0) {
+      hipLaunchKernelGGL(k_trsm64, dim3(rest), dim3(IPX_BLOCK), 0, st, G, (int)M, k);
+      IPX_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_syrk64, dim3(rest * (rest + 1) / 2), dim3(IPX_BLOCK), 0, st, G, (int)M,
+                         k, rest);
+      IPX_CHECK_LAUNCH();
+    }
+  }
+  return IPX_OK;
+}
+
 }  // namespace
 
 int ipx_dense_gemv_launch(int m, int n, const double *A, int64_t lda, const double *x,
@@ -770,7 +799,7 @@ int ipx_chol_factor(int64_t M, double *G, int *flag, double *work, void *stream)
                      st, G, (int)M, work);
   IPX_CHECK_LAUNCH();
   for (int k = 0; k < nb; ++k) {
-    hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(IPX_BLOCK), 0, st, G, (int)M, k, flag, work);
+    hipLaunchKernelGGL(k_potrf64<false>, dim3(1), dim3(IPX_BLOCK), 0, st, G, (int)M, k, flag, work);
     IPX_CHECK_LAUNCH();
     const int rest = nb - k - 1;
     if (rest > 0) {
@@ -789,22 +818,14 @@ int ipx_chol_factor(int64_t M, double *G, int *flag, double *work, void *stream)
 // complement behind them.  The flag is the caller's too (not cleared).
 int ipx_chol_factor_steps(int64_t M, double *G, int64_t steps, int *flag, double *work,
                           void *stream) {
-  if (M < FB || M % FB || steps < 0 || steps > M / FB || !G || !flag || !work) return IPX_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const int nb = (int)(M / FB);
-  for (int k = 0; k < (int)steps; ++k) {
-    hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(IPX_BLOCK), 0, st, G, (int)M, k, flag, work);
-    IPX_CHECK_LAUNCH();
-    const int rest = nb - k - 1;
-    if (rest > 0) {
-      hipLaunchKernelGGL(k_trsm64, dim3(rest), dim3(IPX_BLOCK), 0, st, G, (int)M, k);
-      IPX_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_syrk64, dim3(rest * (rest + 1) / 2), dim3(IPX_BLOCK), 0, st, G, (int)M,
-                         k, rest);
-      IPX_CHECK_LAUNCH();
-    }
-  }
-  return IPX_OK;
+  return chol_factor_steps(k_potrf64<false>, M, G, steps, flag, work, stream);
+}
+
+// The same in skip mode (k_potrf64<true>: a pivot within IPX_PIVOT_RTOL x its entry of zero is a
+// dropped row, +inf on the diagonal over a zero column; k_trsm64 and k_syrk64 as they are).
+int ipx_chol_factor_steps_skip(int64_t M, double *G, int64_t steps, int *flag, double *work,
+                               void *stream) {
+  return chol_factor_steps(k_potrf64<true>, M, G, steps, flag, work, stream);
 }
 
 // X (M x M) <- (L L')^-1 from the factor in the lower triangle of G.  G is used as the

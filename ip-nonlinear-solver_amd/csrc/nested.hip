@@ -68,6 +68,12 @@ __device__ __forceinline__ const double *update_of(const ipx_nd_args &a, const F
 }
 
 // ---------------------------------------------------------------- small fronts
+// SKIP: the pivot-skipping factorization (rank-deficient A; ipsolver/nested.py
+// PivotSkippingNestedSolver).  A pivot with |d| <= IPX_PIVOT_RTOL x its diagonal entry of S --
+// row perm[k] of A depends on the rows eliminated before it, or is zero -- is skipped: its column
+// of L is zero, its diagonal +inf, the trailing matrix takes no update, no bit is raised.  A
+// pivot below -IPX_PIVOT_RTOL x the entry, or a NaN, stays bits 0 | 2.
+template <bool SKIP>
 __global__ void __launch_bounds__(IPX_BLOCK)
 k_nd_factor_small(ipx_nd_args a, int64_t off, int assemble_only) {
   extern __shared__ double lds[];
@@ -105,15 +111,22 @@ k_nd_factor_small(ipx_nd_args a, int64_t off, int assemble_only) {
   for (int k = 0; k < steps; ++k) {
     __syncthreads();
     const double d = F[k * ldl + k];
-    const double lkk = sqrt(d > 0.0 ? d : 1.0);
-    for (int i = k + 1 + tid; i < n; i += IPX_BLOCK) F[i * ldl + k] /= lkk;
+    // (SKIP: every thread reads diag[k] = S_kk here, so thread 0 stores the new diagonal only
+    // behind the barrier)
+    const bool skip = SKIP && fabs(d) <= IPX_PIVOT_RTOL * diag[k];
+    const double lkk = skip ? __builtin_huge_val() : sqrt(d > 0.0 ? d : 1.0);
+    for (int i = k + 1 + tid; i < n; i += IPX_BLOCK) {
+      if (skip) F[i * ldl + k] = 0.0;
+      else F[i * ldl + k] /= lkk;
+    }
     if (tid == 0) {
       // bit 0: the pivot lost 43 bits against its diagonal entry of S (the factorization goes
       // on); bit 2: it is not positive (no factorization)
-      if (!(d > IPX_PIVOT_RTOL * diag[k])) bits |= (d > 0.0) ? 1 : 5;
-      diag[k] = lkk;
+      if (!skip && !(d > IPX_PIVOT_RTOL * diag[k])) bits |= (d > 0.0) ? 1 : 5;
+      if (!SKIP) diag[k] = lkk;
     }
     __syncthreads();
+    if (SKIP && tid == 0) diag[k] = lkk;
     const int rem = n - k - 1;
     for (int e = tid; e < rem * rem; e += IPX_BLOCK) {
       const int i = e / rem, j = e - i * rem;
@@ -229,6 +242,9 @@ k_nd_forward(ipx_nd_args a, int64_t off, const double *__restrict__ w, int xcap)
     if (tid < IPX_WAVE) {
       double xv = tid < nb ? x[kb + tid] : 0.0;
       for (int k = 0; k < nb; ++k) {
+        // A DIVISION, not a multiply by a reciprocal formed elsewhere: a skipped pivot
+        // (pivot-skipping factorization) is stored as +inf over a zero column, and x / inf = 0
+        // for every finite x is what makes this solve the one with the kept rows only.
         const double xk = __shfl(xv, k, IPX_WAVE) / T[k * (TB + 1) + k];
         if (tid == k) xv = xk;
         else if (tid > k && tid < nb) xv -= T[tid * (TB + 1) + k] * xk;
@@ -276,6 +292,8 @@ k_nd_backward(ipx_nd_args a, int64_t off, double *__restrict__ xg, int xcap) {
     if (tid < IPX_WAVE) {
       double xv = tid < nb ? x[kb + tid] : 0.0;
       for (int k = nb - 1; k >= 0; --k) {
+        // (a division on purpose, as in k_nd_forward: x / inf = 0 for a skipped pivot, whose
+        // row's entries in the earlier columns are then multiplied by that zero)
         const double xk = __shfl(xv, k, IPX_WAVE) / T[k * (TB + 1) + k];
         if (tid == k) xv = xk;
         else if (tid < k) xv -= T[k * (TB + 1) + tid] * xk;
@@ -293,6 +311,51 @@ k_nd_backward(ipx_nd_args a, int64_t off, double *__restrict__ xg, int xcap) {
     __syncthreads();
   }
   for (int i = tid; i < f.s; i += IPX_BLOCK) xg[a.perm[f.row0 + i]] = x[i];
+}
+
+// ---------------------------------------------------------------- pivot-skipping: the dropped rows
+// mark[row] = 1 where the stored diagonal of the row's own position is +inf, else 0: a workgroup
+// per front over its own rows (every row of A is an own row of exactly one front)
+__global__ void __launch_bounds__(IPX_BLOCK) k_nd_skipped(ipx_nd_args a, int32_t *mark) {
+  const Front f = front_of(a.sn, (int)blockIdx.x);
+  const double *G = a.fronts + f.off;
+  for (int i = threadIdx.x; i < f.s; i += IPX_BLOCK)
+    mark[a.perm[f.row0 + i]] = G[(int64_t)i * f.ld + i] == __builtin_huge_val() ? 1 : 0;
+}
+
+// t[i] = 0 for a dropped row, else b[i] + sum_j Y[i + m j] b[d_rows[j]] (j ascending)
+__global__ void __launch_bounds__(IPX_BLOCK)
+k_nd_dropped_fold(int64_t m, int q, const double *__restrict__ Y, const int32_t *__restrict__ d_rows,
+                  const int32_t *__restrict__ mark, const double *__restrict__ b,
+                  double *__restrict__ t) {
+  __shared__ double bd[32];
+  if ((int)threadIdx.x < q) bd[threadIdx.x] = b[d_rows[threadIdx.x]];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * IPX_BLOCK + threadIdx.x;
+  if (i >= m) return;
+  double v = 0.0;
+  if (!mark[i]) {
+    v = b[i];
+    for (int j = 0; j < q; ++j) v += Y[i + m * j] * bd[j];
+  }
+  t[i] = v;
+}
+
+// out[i] = u[i] for a kept row; out[d_rows[j]] = sum_g part[g * q + j] (g ascending): the last
+// q threads of the launch, a dropped row each
+__global__ void __launch_bounds__(IPX_BLOCK)
+k_nd_dropped_fill(int64_t m, int q, int groups, const double *__restrict__ part,
+                  const int32_t *__restrict__ d_rows, const int32_t *__restrict__ mark,
+                  const double *__restrict__ u, double *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * IPX_BLOCK + threadIdx.x;
+  if (i < m) {
+    if (!mark[i]) out[i] = u[i];
+  } else if (i < m + q) {
+    const int j = (int)(i - m);
+    double sum = 0.0;
+    for (int g = 0; g < groups; ++g) sum += part[(int64_t)g * q + j];
+    out[d_rows[j]] = sum;
+  }
 }
 
 int bad_args(const ipx_nd_args *a, int64_t off, int64_t cnt) {
@@ -338,27 +401,24 @@ int nd_backward(const ipx_nd_args *a, int64_t off, int64_t cnt, int32_t fmax, do
   return IPX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ipx_nd_small_max(void) { return ND_SMALL_MAX; }
-
-int ipx_nd_factor_small(const ipx_nd_args *a, int64_t off, int64_t cnt, int32_t fmax,
-                        int32_t assemble_only, void *stream) {
+// small fronts of one level with the given kernel (k_nd_factor_small<false> or <true>)
+int nd_factor_small_launch(void (*kernel)(ipx_nd_args, int64_t, int), const ipx_nd_args *a,
+                           int64_t off, int64_t cnt, int32_t fmax, int32_t assemble_only,
+                           void *stream) {
   if (bad_args(a, off, cnt) || fmax < 1 || fmax > ND_SMALL_MAX || !a->A_rowptr || !a->A_val)
     return IPX_EINVAL;
   if (cnt == 0) return IPX_OK;
   const size_t lds = sizeof(double) * ((size_t)fmax * (fmax | 1) + fmax) + sizeof(int) * fmax;
-  if (raise_lds(k_nd_factor_small, lds) != IPX_OK) return IPX_ELAUNCH;
-  hipLaunchKernelGGL(k_nd_factor_small, dim3((unsigned)cnt), dim3(IPX_BLOCK), lds,
-                     (hipStream_t)stream, *a, off, (int)assemble_only);
+  if (raise_lds(kernel, lds) != IPX_OK) return IPX_ELAUNCH;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)cnt), dim3(IPX_BLOCK), lds, (hipStream_t)stream, *a,
+                     off, (int)assemble_only);
   IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
 
-int ipx_nd_factor_large(const ipx_nd_args *a, const int64_t *sn_host, const int32_t *lists_host,
-                        int64_t off, int64_t cnt, int32_t assemble_only, void *stream) {
+// large fronts of one level; skip: the pivot-skipping diagonal-tile kernel
+int nd_factor_large(const ipx_nd_args *a, const int64_t *sn_host, const int32_t *lists_host,
+                    int64_t off, int64_t cnt, int32_t assemble_only, int skip, void *stream) {
   if (bad_args(a, off, cnt) || !sn_host || !lists_host || !a->work || !a->A_rowptr || !a->A_val ||
       cnt > 65535)
     return IPX_EINVAL;
@@ -380,14 +440,72 @@ int ipx_nd_factor_large(const ipx_nd_args *a, const int64_t *sn_host, const int3
   }
   for (int64_t t = 0; t < cnt && !assemble_only; ++t) {
     const Front f = front_of(sn_host, lists_host[off + t]);
-    const int rc = ipx_chol_factor_steps(f.ld, a->fronts + f.off, (f.s + f.pad) / TB,
-                                         reinterpret_cast<int *>(a->flag), a->work + f.work, stream);
+    const int rc = (skip ? ipx_chol_factor_steps_skip : ipx_chol_factor_steps)(
+        f.ld, a->fronts + f.off, (f.s + f.pad) / TB, reinterpret_cast<int *>(a->flag),
+        a->work + f.work, stream);
     if (rc != IPX_OK) return rc;
   }
   if (!assemble_only) {
     hipLaunchKernelGGL(k_nd_mirror, dim3(256, (unsigned)cnt), dim3(IPX_BLOCK), 0, st, *a, off);
     IPX_CHECK_LAUNCH();
   }
+  return IPX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ipx_nd_small_max(void) { return ND_SMALL_MAX; }
+
+int ipx_nd_factor_small(const ipx_nd_args *a, int64_t off, int64_t cnt, int32_t fmax,
+                        int32_t assemble_only, void *stream) {
+  return nd_factor_small_launch(k_nd_factor_small<false>, a, off, cnt, fmax, assemble_only, stream);
+}
+
+int ipx_nd_factor_small_skip(const ipx_nd_args *a, int64_t off, int64_t cnt, int32_t fmax,
+                             int32_t assemble_only, void *stream) {
+  return nd_factor_small_launch(k_nd_factor_small<true>, a, off, cnt, fmax, assemble_only, stream);
+}
+
+int ipx_nd_factor_large(const ipx_nd_args *a, const int64_t *sn_host, const int32_t *lists_host,
+                        int64_t off, int64_t cnt, int32_t assemble_only, void *stream) {
+  return nd_factor_large(a, sn_host, lists_host, off, cnt, assemble_only, 0, stream);
+}
+
+int ipx_nd_factor_large_skip(const ipx_nd_args *a, const int64_t *sn_host,
+                             const int32_t *lists_host, int64_t off, int64_t cnt,
+                             int32_t assemble_only, void *stream) {
+  return nd_factor_large(a, sn_host, lists_host, off, cnt, assemble_only, 1, stream);
+}
+
+int ipx_nd_skipped(const ipx_nd_args *a, int32_t *mark, void *stream) {
+  if (bad_args(a, 0, 0) || !mark) return IPX_EINVAL;
+  if (a->nsuper == 0) return IPX_OK;
+  hipLaunchKernelGGL(k_nd_skipped, dim3((unsigned)a->nsuper), dim3(IPX_BLOCK), 0,
+                     (hipStream_t)stream, *a, mark);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+int ipx_nd_dropped_fold(int64_t m, int32_t q, const double *Y, const int32_t *d_rows,
+                        const int32_t *mark, const double *b, double *t, void *stream) {
+  if (m < 1 || q < 0 || q > 32 || !mark || !b || !t || (q > 0 && (!Y || !d_rows)))
+    return IPX_EINVAL;
+  hipLaunchKernelGGL(k_nd_dropped_fold, dim3((unsigned)((m + IPX_BLOCK - 1) / IPX_BLOCK)),
+                     dim3(IPX_BLOCK), 0, (hipStream_t)stream, m, (int)q, Y, d_rows, mark, b, t);
+  IPX_CHECK_LAUNCH();
+  return IPX_OK;
+}
+
+int ipx_nd_dropped_fill(int64_t m, int32_t q, const double *part, const int32_t *d_rows,
+                        const int32_t *mark, const double *u, double *out, void *stream) {
+  if (m < 1 || q < 1 || q > 32 || !part || !d_rows || !mark || !u || !out) return IPX_EINVAL;
+  const int groups = ipx_border_groups(m);
+  hipLaunchKernelGGL(k_nd_dropped_fill, dim3((unsigned)((m + q + IPX_BLOCK - 1) / IPX_BLOCK)),
+                     dim3(IPX_BLOCK), 0, (hipStream_t)stream, m, (int)q, groups, part, d_rows, mark,
+                     u, out);
+  IPX_CHECK_LAUNCH();
   return IPX_OK;
 }
 

@@ -178,6 +178,12 @@ _SIGNATURES = {
     "ipx_nd_factor_large": [_P, _P, _P, _I64, _I64, _I32, _P],
     "ipx_nd_solve": [_P, _I32, _P, _P, _P, _P],
     "ipx_chol_factor_steps": [_I64, _P, _I64, _P, _P, _P],
+    "ipx_nd_factor_small_skip": [_P, _I64, _I64, _I32, _I32, _P],
+    "ipx_nd_factor_large_skip": [_P, _P, _P, _I64, _I64, _I32, _P],
+    "ipx_chol_factor_steps_skip": [_I64, _P, _I64, _P, _P, _P],
+    "ipx_nd_skipped": [_P, _P, _P],
+    "ipx_nd_dropped_fold": [_I64, _I32, _P, _P, _P, _P, _P, _P],
+    "ipx_nd_dropped_fill": [_I64, _I32, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                             _I32, _P, _P],
 }

@@ -439,7 +439,7 @@ def minimize_constrained(fun, x0, grad, hess='2-point', constraints=(), method=N
                                        sparse_jacobian, options, callback, max_iter, verbose)
     # the solver behind the projections the run was handed last, made then or reused from a
     # cache ("BoxSchurNormalSolver/<inner>" for the box-Schur elimination, "SVDProjector" after
-    # the SVD exit; None when this process's projector factored nothing: no constraint rows, or
+    # the SVD exit, "PivotSkippingNestedSolver" after the device exit for sparse Jacobians; None when this process's projector factored nothing: no constraint rows, or
     # a row-sharded backend that builds its solvers itself).
     # An attribute, not a key: ``result.keys()`` stays the reference's set of fields.
     object.__setattr__(result, "normal_solver", projector.last_normal_solver())
@@ -478,6 +478,11 @@ def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, 
         raise NotImplementedError("rank_deficient=%r: the row-sharded backend builds its own "
                                   "(A A')^-1 solvers; the option is available on one GPU only"
                                   % (rank_def,))
+    sparse_def = solver_options.current().sparse_rank_deficient
+    if sparse_def != "host-svd" and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
+        raise NotImplementedError("sparse_rank_deficient=%r: the row-sharded backend builds its "
+                                  "own (A A')^-1 solvers; the option is available on one GPU only"
+                                  % (sparse_def,))
     if _qn.is_strategy(hess) and (shard or (hasattr(x0, "sh") and hasattr(x0, "owns"))):
         raise NotImplementedError("hess=%r: quasi-Newton Hessians are not available on the "
                                   "row-sharded backend; pass an exact Hessian or finite "

@@ -163,6 +163,7 @@ class NestedDissectionNormalSolver:
     SMALL_FRONT = 128            # the cut between the two paths (at most ipx_nd_small_max())
     FRONT_MAX = 2048             # no front larger than this
     MAX_BYTES = 2 << 30          # device storage: fronts (factor and updates), vectors, tables
+    _FACTOR = ("ipx_nd_factor_small", "ipx_nd_factor_large")    # the entry of either path
 
     def __init__(self, A):
         lib = _hip.load()
@@ -211,9 +212,9 @@ class NestedDissectionNormalSolver:
         a, st, plan = ctypes.byref(self.args), stream_ptr(), self.plan
         at, nsm, fsm, nlg, _ = plan.levels[lv]
         if nsm:
-            _hip.call("ipx_nd_factor_small", a, at, nsm, fsm, assemble_only, st)
+            _hip.call(self._FACTOR[0], a, at, nsm, fsm, assemble_only, st)
         if nlg:
-            _hip.call("ipx_nd_factor_large", a, _host_ptr(plan.sn), _host_ptr(plan.lists),
+            _hip.call(self._FACTOR[1], a, _host_ptr(plan.sn), _host_ptr(plan.lists),
                       at + nsm, nlg, assemble_only, st)
 
     def assemble_level(self, lv):
@@ -246,6 +247,28 @@ class NestedDissectionNormalSolver:
                   _p(w.t), _p(out), stream_ptr())
         self.stats["solves"] += 1
         return DVec(out)
+
+
+class PivotSkippingNestedSolver(NestedDissectionNormalSolver):
+    """The same factorization in skip mode, for a rank-deficient A: a pivot within 2^-43 of its
+    diagonal entry of zero is a row of A that depends on the rows eliminated before it (or a zero
+    row); it is dropped -- a zero column of L under a diagonal stored as +inf.  What is factored is
+    ``A_S A_S'``, S the kept rows, and ``solve(w)`` returns ``(A_S A_S')^-1 w_S`` on S and exactly
+    0 on the dropped rows, whatever ``w`` holds there (the solve kernels divide by the diagonal:
+    x / inf = 0).  ``dropped``: the dropped rows, ascending (host); ``rank = m - len(dropped)``;
+    ``mark``: 1 at a dropped row (device int32).  The analysis, the plan and the limits
+    (``NestedDissectionRefused``) are the base class's; a negative pivot or a NaN is still
+    ``LinAlgError``."""
+
+    _FACTOR = ("ipx_nd_factor_small_skip", "ipx_nd_factor_large_skip")
+
+    def _factor(self):
+        NestedDissectionNormalSolver._factor(self)
+        self.mark = torch.empty(self.m, dtype=torch.int32, device=self.ws.device)
+        _hip.call("ipx_nd_skipped", ctypes.byref(self.args), _p(self.mark), stream_ptr())
+        self.dropped = np.flatnonzero(self.mark.cpu().numpy()).astype(np.int32)   # (the one read)
+        self.rank = self.m - len(self.dropped)
+        self.stats["dropped"] = len(self.dropped)
 
 
 def nested_dissection_solver(A):

@@ -23,7 +23,10 @@ reference's own exit: a warning and the SVD projections (projections.py:101-108,
 the reference, its factors are uploaded once and every operator application is device
 matvecs (``SVDProjector``).  Under the option ``rank_deficient = "pivoted-qr"`` a dense device
 Jacobian with ``1 <= m <= n`` stays on the device instead: a column-pivoted QR and a complete
-orthogonal decomposition (``DenseCODProjector``, dense_cod.py).
+orthogonal decomposition (``DenseCODProjector``, dense_cod.py).  Under the option
+``sparse_rank_deficient = "skip-pivots"`` a sparse Jacobian stays on the device too: the
+nested-dissection Cholesky in pivot-skipping mode and a Woodbury correction over the dropped rows
+(``SparseDeficientProjector``, sparse_deficient.py).
 """
 from warnings import warn
 
@@ -40,6 +43,7 @@ from .dense import DenseNormalSolver, DeviceDense
 from .factored_projector import FactoredProjector, _Op, operator_triple  # noqa: F401
 from .dense_qr import DenseQRProjector
 from .dense_cod import DenseCODProjector
+from .sparse_deficient import SparseDeficientProjector
 from .device_mode import RowSelection
 # The solvers, their selection and its options live in modules of their own, layered
 #   solver_options < banded < blocktri, blockwide, iterative, nested < band_solver < bordered
@@ -55,14 +59,15 @@ from .solver_options import (WIDE_BAND_POLICIES, wide_band, border_columns, link
                              DENSE_FACTORIZATIONS, dense_factorization,
                              dense_factorization_choice, check_dense_factorization,
                              RANK_DEFICIENT, rank_deficient, rank_deficient_choice,
-                             check_rank_deficient)
+                             check_rank_deficient, SPARSE_RANK_DEFICIENT, sparse_rank_deficient,
+                             sparse_rank_deficient_choice, check_sparse_rank_deficient)
 from .banded import (BandedNormalSolver, BandedNotDecoupled, HANDLE_STATS, _Symbolic,  # noqa: F401
                      _SYMBOLIC_ATTR, _symbolic_for, half_bandwidth_of_aat)
 from .blocktri import BlockTridiagonalNormalSolver, block_size  # noqa: F401
 from .blockwide import WideBlockTridiagonalNormalSolver  # noqa: F401
 from .iterative import IterativeNormalSolver, PcgArgs  # noqa: F401
 from .nested import (NestedDissectionNormalSolver, NestedDissectionRefused,  # noqa: F401
-                     nested_dissection_solver)
+                     PivotSkippingNestedSolver, nested_dissection_solver)
 from .band_solver import border_reach, direct_band_solver, direct_solver_class  # noqa: F401
 from .bordered import (BorderedNormalSolver, BorderedRefused, border_split,  # noqa: F401
                        bordered_solver, _border_split_for)
@@ -77,7 +82,7 @@ _F64 = torch.float64
 
 def note_solver(ops):
     P = getattr(ops[0], "projector", None)
-    if isinstance(P, NormalEquationProjector):
+    if isinstance(P, (NormalEquationProjector, SparseDeficientProjector)):
         _last_solver[0] = solver_name(P.solver)
     else:
         _last_solver[0] = None if P is None else type(P).__name__
@@ -379,7 +384,13 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
     m, n = A.shape
     if method == "SVDFactorization":
         return SVDProjector(A, orth_tol, max_refin, tol).operators()
-    A_caller, row_perm = A, None
+    A_caller, row_perm, solver = A, None, None
+    # the device exit for a rank-deficient sparse Jacobian (whatever ``sparse_direct`` says: that
+    # option decides the first attempt only)
+    skip_pivots = sparse and m >= 1 \
+        and solver_options.current().sparse_rank_deficient == "skip-pivots"
+    ill = ("Ill-conditioned Jacobian matrix (a pivot of A A' lost 43 bits); too large for "
+           "the dense SVD fallback: keeping the factorization under iterative refinement.")
     try:
         if sparse and m > 0:
             # A A' banded only after a reordering of the rows (equality rows stacked on
@@ -399,10 +410,9 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
                                       else normal_solver_for(A, deferred))
         inner = getattr(solver, "inner", solver)           # (box-Schur: its banded Schur solve)
         if getattr(inner, "ill_conditioned", False):
-            if m * n <= SVDProjector.MAX_ELEMENTS:
+            if skip_pivots or m * n <= SVDProjector.MAX_ELEMENTS:
                 raise np.linalg.LinAlgError("numerically rank deficient")
-            warn("Ill-conditioned Jacobian matrix (a pivot of A A' lost 43 bits); too large for "
-                 "the dense SVD fallback: keeping the factorization under iterative refinement.")
+            warn(ill)
     except np.linalg.LinAlgError:
         # the reference's exits: projections.py:101-108 (sparse), :181-187 (dense)
         if solver_options.current().rank_deficient == "pivoted-qr" \
@@ -412,6 +422,20 @@ def _projections(A, method, orth_tol, max_refin, tol, deferred=None):
             warn("Singular Jacobian matrix. Using a pivoted QR decomposition on the device to "
                  "perform the factorizations.")
             return DenseCODProjector(A_caller, orth_tol, max_refin).operators()
+        if skip_pivots:
+            try:
+                P = SparseDeficientProjector(A_caller, orth_tol, max_refin)
+            except (NestedDissectionRefused, np.linalg.LinAlgError):
+                P = None         # past the nested solver's limits, or more than 32 dropped rows
+            if P is not None:
+                warn("Singular Jacobian matrix. Using a pivot-skipping sparse Cholesky "
+                     "factorization on the device to perform the factorizations.")
+                return P.operators()
+            if solver is not None and m * n > SVDProjector.MAX_ELEMENTS:
+                # (``ill_conditioned`` past the host exit's cap: as without the option)
+                warn(ill)
+                return NormalEquationProjector(A, solver, orth_tol, max_refin, row_perm=row_perm,
+                                               lazy_norm=deferred is not None).operators()
         warn("Singular Jacobian matrix. Using dense SVD decomposition to perform the "
              "factorizations." if sparse else
              "Singular Jacobian matrix. Using SVD decomposition to perform the "

@@ -31,6 +31,14 @@ a dense device Jacobian with ``1 <= m <= n`` is factored by a column-pivoted QR 
 instead (``DenseCODProjector``, dense_cod.py) -- sparse Jacobians, ``m > n`` and
 ``method="SVDFactorization"`` keep the host exit.  Held and keyed like ``iterative_precond``.
 
+``sparse_rank_deficient``: "host-svd" (default): a SPARSE Jacobian found rank deficient takes the
+host exit above (capped at ``m n <= 2^25`` elements); "skip-pivots": it is factored once more on
+the device by the nested-dissection Cholesky in pivot-skipping mode, whatever ``sparse_direct``
+says, and the pseudo-inverse operators come from that factorization and a Woodbury correction over
+the dropped rows (``SparseDeficientProjector``, sparse_deficient.py) -- more than 32 dropped rows,
+a matrix past the nested solver's limits and ``method="SVDFactorization"`` keep the host exit.
+Held and keyed like ``iterative_precond``.
+
 Scoped: ``with scoped(wide_band="block-tridiagonal", link_rows=4): ...`` holds any subset for the
 duration of the block.  ``current().key()`` is part of the key of every cached factorization: a
 new option is a new name here (``NAMES``, ``check``, ``key``) and nowhere else.
@@ -47,11 +55,13 @@ ITERATIVE_PRECONDS = ("block", "compact", "two-level")
 SPARSE_DIRECT = ("off", "nested-dissection")
 DENSE_FACTORIZATIONS = ("normal-equations", "householder-qr")
 RANK_DEFICIENT = ("host-svd", "pivoted-qr")
+SPARSE_RANK_DEFICIENT = ("host-svd", "skip-pivots")
 NAMES = ("wide_band", "border_columns", "link_rows", "iterative_precond", "sparse_direct",
-         "dense_factorization", "rank_deficient")
+         "dense_factorization", "sparse_rank_deficient", "rank_deficient")
 # the options held beside the tuple: name -> allowed values, the first the default
 _BESIDE = {"iterative_precond": ITERATIVE_PRECONDS, "sparse_direct": SPARSE_DIRECT,
-           "dense_factorization": DENSE_FACTORIZATIONS, "rank_deficient": RANK_DEFICIENT}
+           "dense_factorization": DENSE_FACTORIZATIONS, "rank_deficient": RANK_DEFICIENT,
+           "sparse_rank_deficient": SPARSE_RANK_DEFICIENT}
 
 
 class Options(collections.namedtuple("Options", "wide_band border_columns link_rows")):
@@ -59,15 +69,17 @@ class Options(collections.namedtuple("Options", "wide_band border_columns link_r
     sparse_direct = SPARSE_DIRECT[0]
     dense_factorization = DENSE_FACTORIZATIONS[0]
     rank_deficient = RANK_DEFICIENT[0]
+    sparse_rank_deficient = SPARSE_RANK_DEFICIENT[0]
 
     def __new__(cls, wide_band, border_columns, link_rows, iterative_precond="block",
                 sparse_direct="off", dense_factorization="normal-equations",
-                rank_deficient="host-svd"):
+                rank_deficient="host-svd", sparse_rank_deficient="host-svd"):
         self = super().__new__(cls, wide_band, border_columns, link_rows)
         self.iterative_precond = iterative_precond
         self.sparse_direct = sparse_direct
         self.dense_factorization = dense_factorization
         self.rank_deficient = rank_deficient
+        self.sparse_rank_deficient = sparse_rank_deficient
         return self
 
     def _replace(self, **changes):
@@ -86,6 +98,8 @@ class Options(collections.namedtuple("Options", "wide_band border_columns link_r
             extra += (self.dense_factorization,)
         if self.rank_deficient != RANK_DEFICIENT[0]:
             extra += (self.rank_deficient,)
+        if self.sparse_rank_deficient != SPARSE_RANK_DEFICIENT[0]:
+            extra += (self.sparse_rank_deficient,)
         return tuple(self) + extra
 
 
@@ -133,9 +147,9 @@ def pop_from(options):
     that is not given: the value in force), as the keywords of ``scoped``."""
     held = {name: check(name, options.pop(name, getattr(current(), name)))
             for name in NAMES[:4]}
-    # (``sparse_direct``, ``dense_factorization`` and ``rank_deficient`` only when given: without
-    # it ``scoped`` leaves the value in force as it is, and the record of a call that does not
-    # use it reads as before the option)
+    # (``sparse_direct``, ``dense_factorization``, ``sparse_rank_deficient`` and
+    # ``rank_deficient`` only when given: without it ``scoped`` leaves the value in force as it
+    # is, and the record of a call that does not use it reads as before the option)
     for name in NAMES[4:]:
         if name in options:
             held[name] = check(name, options.pop(name))
@@ -165,3 +179,5 @@ sparse_direct, sparse_direct_choice, check_sparse_direct = _wrappers("sparse_dir
 dense_factorization, dense_factorization_choice, check_dense_factorization = \
     _wrappers("dense_factorization")
 rank_deficient, rank_deficient_choice, check_rank_deficient = _wrappers("rank_deficient")
+sparse_rank_deficient, sparse_rank_deficient_choice, check_sparse_rank_deficient = \
+    _wrappers("sparse_rank_deficient")
