@@ -165,7 +165,8 @@ int ipx_fold2(const double *partial, int32_t count, double *red, const double *g
 
 /* ---- dense Jacobian path (projections.py:175-233 QR; here Gram + Cholesky).
  * A is row-major with leading dimension lda.  ipx_dense_gemv mirrors
- * ipx_csr_spmv's fused epilogue.  G / X are M x M, M = ipx_dense_padded(m). */
+ * ipx_csr_spmv's fused epilogue (diag only for m == n, IPX_EINVAL otherwise: diag_r pairs
+ * with x_r).  G / X are M x M, M = ipx_dense_padded(m). */
 int ipx_dense_gemv(int64_t m, int64_t n, const double *A, int64_t lda, const double *x,
                    double alpha, const double *diag, double beta, const double *yin,
                    double *yout, double *red, double *ws, void *stream);

@@ -677,6 +677,9 @@ int ipx_dense_gemv(int64_t m, int64_t n, const double *A, int64_t lda, const dou
                    double alpha, const double *diag, double beta, const double *yin,
                    double *yout, double *red, double *ws, void *stream) {
   if (m < 0 || n < 0 || !A || !x || !yout || lda < n) return IPX_EINVAL;
+  // diag_r pairs with x_r: only a square product has one for every row (ipx_csr_spmv refuses
+  // the same; with m > n the kernel would read past x)
+  if (diag && m != n) return IPX_EINVAL;
   if (m == 0) {
     if (red) (void)hipMemsetAsync(red, 0, 2 * sizeof(double), (hipStream_t)stream);
     return IPX_OK;

@@ -23,11 +23,19 @@ struct OpFill {
   double v;
   __device__ double operator()(int64_t) const { return v; }
 };
+// np.maximum / np.minimum: a NaN operand is the result (the first one when both are), where
+// fmax / fmin alone would drop it; every other pair of operands gets fmax / fmin's bits.
+__device__ __forceinline__ double np_maximum(double a, double b) {
+  return a != a ? a : (b != b ? b : fmax(a, b));
+}
+__device__ __forceinline__ double np_minimum(double a, double b) {
+  return a != a ? a : (b != b ? b : fmin(a, b));
+}
 struct OpClip {
   const double *x, *lb, *ub;
   __device__ double operator()(int64_t i) const {
     // np.minimum(np.maximum(x, lb), ub)
-    return fmin(fmax(x[i], lb[i]), ub[i]);
+    return np_minimum(np_maximum(x[i], lb[i]), ub[i]);
   }
 };
 struct OpAffine {
@@ -46,7 +54,7 @@ struct OpGather {   // out[i] = sign[i] * (x[idx[i]] - shift[i])
 
 struct OpMaxScalar {   // np.maximum(x, c)
   const double *x; double c;
-  __device__ double operator()(int64_t i) const { return fmax(x[i], c); }
+  __device__ double operator()(int64_t i) const { return np_maximum(x[i], c); }
 };
 struct OpWherePos {    // np.where(v > 0, a, c)
   const double *v, *a; double c;
@@ -113,6 +121,9 @@ struct RedDot {
   __device__ void init(Acc<1> &a) const { a.v[0] = 0.0; }
   __device__ void step(Acc<1> &a, int64_t i) const { a.v[0] += x[i] * y[i]; }
 };
+// The maximum drops a NaN entry (fmax here and in the shared folds); the sum of squares is NaN
+// exactly when an entry is, and the callers that want numpy's norm(., inf) take the NaN from it
+// (ipsolver/device.py: sumsq_amax, ScalarPack.norm_inf).
 struct RedNorms {   // sum of squares, max |x|
   static constexpr int NQ = 2;
   const double *x;

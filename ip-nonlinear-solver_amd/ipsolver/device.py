@@ -292,18 +292,27 @@ class DVec:
         return val
 
     def sumsq_amax(self):
+        """[sum x^2, max |x|]; max |x| is NaN when an entry is (``_nan_amax``)."""
         c = ctx()
         n = len(self)
         g = _reduce_grid(n)
         off = c.partials(2 * g) if n > 0 else None
         if off is None:
             _hip.call("ipx_norms", n, _p(self.t), _p(c.out), _p(c.ws), stream_ptr())
-            return _read(2)
+            vals = _read(2)
+            return [vals[0], _nan_amax(vals[0], vals[1])]
         _hip.call("ipx_norms_partials", n, _p(self.t), c.parts.data_ptr() + 8 * off, stream_ptr())
         vals = read_folded([(off, g, SUM), (off + g, g, MAX)])
         if c.open_pack is None or c.open_pack() is None:
             c.parts_used = 0
-        return vals
+        return [vals[0], _nan_amax(vals[0], vals[1])]
+
+
+def _nan_amax(sumsq, amax):
+    """``max |x|`` as numpy's ``norm(x, inf)`` has it: NaN when an entry of x is.  The kernels'
+    maximum (fmax, in the reduction and in every fold) drops a NaN entry; their sum of squares --
+    squares are not negative, so no inf - inf -- is NaN exactly when an entry is."""
+    return sumsq if sumsq != sumsq else amax
 
 
 class DeviceScalar:
@@ -393,12 +402,16 @@ class ScalarPack:
             self._claim()
             _hip.call("ipx_norms_partials", len(v), _p(v.t), self.c.parts.data_ptr() + 8 * off,
                       stream_ptr())
-            self.how.append((("fold", len(self.folds)), "sqrt" if which == 0 else None))
+            # (the maximum is read with its sum of squares: where the NaN of an entry shows)
+            self.how.append((("fold", len(self.folds)),
+                             "sqrt" if which == 0 else ("amax", ("fold", len(self.folds) + 1))))
             self.folds.append((off, g, SUM) if which == 0 else (off + g, g, MAX))
+            if which == 1:
+                self.folds.append((off, g, SUM))
         else:
             ptr, base = self._slot(2)
             _hip.call("ipx_norms", len(v), _p(v.t), ptr, _p(self.c.ws), stream_ptr())
-            self.how.append((base + which, "sqrt" if which == 0 else None))
+            self.how.append((base + which, "sqrt" if which == 0 else ("amax", base)))
         return len(self.how) - 1
 
     def norm(self, v):
@@ -452,15 +465,20 @@ class ScalarPack:
         if self.c.open_pack is not None and self.c.open_pack() is self:
             self.c.open_pack = None
             self.c.parts_used = 0
+        def value(slot):
+            return folded[slot[1]] if isinstance(slot, tuple) else vals[slot]
+
         out = []
         for slot, post in self.how:
             if slot is None:
                 v = 0.0
-            elif isinstance(slot, tuple):
-                v = folded[slot[1]]
             else:
-                v = vals[slot]
-            out.append(float(np.sqrt(v)) if post == "sqrt" else v)
+                v = value(slot)
+            if post == "sqrt":
+                v = float(np.sqrt(v))
+            elif post is not None:                 # ("amax", where its sum of squares is)
+                v = _nan_amax(value(post[1]), v)
+            out.append(v)
         return out
 
 
