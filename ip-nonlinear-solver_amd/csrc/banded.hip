@@ -1867,12 +1867,16 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
     if (wg == 0 && tid == 0) { rgX = J.xs_comp[IPX_RG_X]; rgQ = J.xs_comp[IPX_RG_Q]; }
   }
   // p'Hp partials: the loads of ipx_fold_regs<1, FU>::load in a workgroup of FW lanes
+  // (every access below: a base advanced to the window, the span or the own variables -- the
+  // same in every lane -- and an unsigned lane offset clamped against the workgroup's count:
+  // ipx_at)
   double ft[FU];
   if (!PRIME && tid < FW) {
+    const unsigned plast = (unsigned)max(J.np1 - 1, 0);
 #pragma unroll
     for (int u = 0; u < FU; ++u) {
       const int i = tid + u * FW;
-      const double ld = J.p1[max(min(i, J.np1 - 1), 0)];
+      const double ld = ipx_at(J.p1, min((unsigned)i, plast));
       ft[u] = i < J.np1 ? ld : 0.0;
     }
   }
@@ -1881,30 +1885,36 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
   const int64_t g0 = (int64_t)wg * rows_wg - H;      // global row of window row 0
   // r and H p over the span
   double sr[QSP], sh[QSP];
+  {
+    const int64_t cb = min((int64_t)c_lo, J.n - 1);  // (c_lo itself wherever the span has a column)
+    const unsigned slast = (unsigned)max(min((int64_t)nspan, J.n - cb) - 1, (int64_t)0);
 #pragma unroll
-  for (int k = 0; k < QSP; ++k) {
-    const int64_t col = min((int64_t)c_lo + max(min(tid + k * TB, nspan - 1), 0), J.n - 1);
-    sr[k] = J.r_in[col];
-    sh[k] = PRIME ? 0.0 : J.Hp[col];
+    for (int k = 0; k < QSP; ++k) {
+      const unsigned j = min((unsigned)(tid + k * TB), slast);
+      sr[k] = ipx_at(J.r_in + cb, j);
+      sh[k] = PRIME ? 0.0 : ipx_at(J.Hp + cb, j);
+    }
   }
   // window row tid: its entries of A, its band entries
   const int64_t grow = g0 + tid;
   const bool row_in = tid < R && grow >= 0 && grow < m;
-  const int64_t gc = min(max(grow, (int64_t)0), (int64_t)m - 1);
-  const int first = J.A_rowfirst[gc] - c_lo;
+  // (rows of A and of the band counted from the window's first row inside the matrix)
+  const int64_t gb = max(g0, (int64_t)0);
+  const unsigned gc = min((unsigned)max(tid - (int)(gb - g0), 0), (unsigned)max(m - 1 - gb, (int64_t)0));
+  const int first = ipx_at(J.A_rowfirst + gb, gc) - c_lo;
   double av[RLA];
   int ao[RLA];
 #pragma unroll
   for (int k = 0; k < RLA; ++k) {
     av[k] = 0.0; ao[k] = 0;
     if (k < J.rl) {                                   // (uniform)
-      av[k] = J.A_ell_val[(int64_t)k * m + gc];
-      ao[k] = CONTIG ? k : (int)J.A_ell_off16[(int64_t)k * m + gc];
+      av[k] = ipx_at(J.A_ell_val + ((int64_t)k * m + gb), gc);
+      ao[k] = CONTIG ? k : (int)ipx_at(J.A_ell_off16 + ((int64_t)k * m + gb), gc);
     }
   }
   double a[1], b[1], d[1];
   {
-    const double bv = band[gc], avv = band[(int64_t)m + gc];
+    const double bv = ipx_at(band + gb, gc), avv = ipx_at(band + ((int64_t)m + gb), gc);
     a[0] = (row_in && grow >= 1 && tid >= 1) ? avv : 0.0;      // (row 0 of the window: cut)
     b[0] = row_in ? bv : 1.0;
   }
@@ -1975,16 +1985,18 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
   unsigned ac[QP];
   v2d aw0[QP], aw1[QP], ax[XN == 0 ? QP : 1], ap[XN == 0 ? QP : 1];
   {
+    // (pair tid + k TB of the workgroup, counted from its first pair vb)
     const int64_t last = max((int64_t)av0 + avn - 1, vb) & ~(int64_t)1;
+    const unsigned plast = (unsigned)((last - vb) >> 1);
 #pragma unroll
     for (int k = 0; k < QP; ++k) {
-      const int64_t j = min(vb + 2 * (int64_t)(tid + k * TB), last);
-      ac[k] = *reinterpret_cast<const unsigned *>(J.ell_row + j);
-      aw0[k] = *reinterpret_cast<const v2d *>(J.ell_val + j);
-      aw1[k] = *reinterpret_cast<const v2d *>(J.ell_val + J.n + j);
+      const unsigned jp = min((unsigned)(tid + k * TB), plast);
+      ac[k] = ipx_at(reinterpret_cast<const unsigned *>(J.ell_row + vb), jp);
+      aw0[k] = ipx_at(reinterpret_cast<const v2d *>(J.ell_val + vb), jp);
+      aw1[k] = ipx_at(reinterpret_cast<const v2d *>(J.ell_val + J.n + vb), jp);
       if constexpr (XN == 0) {
-        ax[k] = *reinterpret_cast<const v2d *>(J.x + j);
-        ap[k] = *reinterpret_cast<const v2d *>(J.p + j);
+        ax[k] = ipx_at(reinterpret_cast<const v2d *>(J.x + vb), jp);
+        ap[k] = ipx_at(reinterpret_cast<const v2d *>(J.p + vb), jp);
       }
     }
   }
@@ -2011,33 +2023,41 @@ k_step1_solve_tail(int m, int rows_wg, int L, int nwin, const double *__restrict
   if (tid < R) {
     const double xv = d[0] / b[0];
     sx[tid] = xv;
-    if (tid >= H && tid < H + rows_wg && grow < m) J.v[grow] = xv;
+    // (an own row: window row tid - H of the rows from wg rows_wg on)
+    if (tid >= H && tid < H + rows_wg && grow < m)
+      ipx_at(J.v + (int64_t)wg * rows_wg, tid - H) = xv;
   }
   ipx_lds_barrier();
   // ---- g = r_next - A'v on this workgroup's variables (PcrPairTail::apply, r_next out of LDS)
   double gacc = 0.0, xacc = 0.0;
+  // variable vb + jr of the pair: span column jr + dspan (dspan cut to where every pair of the
+  // workgroup clamps to the same end of the span as with the uncut distance), own where
+  // jr - down < avn
+  const int jmax = 2 * QP * TB;
+  const int dspan = (int)min(max(vb - c_lo, (int64_t)-(jmax + 1)), (int64_t)IPX_FP_SPAN);
+  const unsigned down = (unsigned)(av0 - vb);
 #pragma unroll
   for (int k = 0; k < QP; ++k) {
-    const int64_t j = vb + 2 * (int64_t)(tid + k * TB);
+    const unsigned jr = 2u * (unsigned)(tid + k * TB);
     const int c0 = H + (int)(ac[k] & 0xffffu), c1 = H + (int)(ac[k] >> 16);
-    const int s0 = (int)min(max(j - c_lo, (int64_t)0), (int64_t)nspan - 1);
-    const int s1 = (int)min(max(j + 1 - c_lo, (int64_t)0), (int64_t)nspan - 1);
+    const int s0 = min(max((int)jr + dspan, 0), nspan - 1);
+    const int s1 = min(max((int)jr + 1 + dspan, 0), nspan - 1);
     const double sg = PRIME ? J.sign : 1.0;
     double y0 = -sg * (aw0[k].x * sx[c0] + aw1[k].x * sx[c0 + 1]);
     y0 += sg * span[s0];
     double y1 = -sg * (aw0[k].y * sx[c1] + aw1[k].y * sx[c1 + 1]);
     y1 += sg * span[s1];
-    const bool in0 = j >= av0 && j < (int64_t)av0 + avn;
-    const bool in1 = j + 1 >= av0 && j + 1 < (int64_t)av0 + avn;
+    const bool in0 = jr - down < (unsigned)avn;        // (jr < down wraps: not own)
+    const bool in1 = jr + 1 - down < (unsigned)avn;
     if (in0 && in1) {
-      *reinterpret_cast<v2d *>(J.g_out + j) = (v2d){y0, y1};
+      ipx_at(reinterpret_cast<v2d *>(J.g_out + vb), jr >> 1) = (v2d){y0, y1};
       gacc += y0 * y0;
       gacc += y1 * y1;
     } else if (in0) {
-      J.g_out[j] = y0;
+      ipx_at(J.g_out + vb, jr) = y0;
       gacc += y0 * y0;
     } else if (in1) {
-      J.g_out[j + 1] = y1;
+      ipx_at(J.g_out + vb, jr + 1) = y1;
       gacc += y1 * y1;
     }
     if constexpr (XN == 0) {

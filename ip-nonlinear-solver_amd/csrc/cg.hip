@@ -766,40 +766,73 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
 #pragma unroll
   for (int q = 0; q < Q; ++q)
     dg[q] = HAS_DIAG ? diag[r0 + min(tid + q * IPX_BLOCK, nrows - 1)] : 0.0;
+  // a tile whose rows all have rl entries: row i's products are prod[i rl .. i rl + rl), no
+  // row pointers, in memory or in LDS (a workgroup-uniform test, behind the prologue's loads)
+  const bool uniform = C16 && rl >= 0;
   int rpv[Q + 1];
-  if (C16 && rl >= 0) {
-#pragma unroll
-    for (int q = 0; q <= Q; ++q) rpv[q] = min(tid + q * IPX_BLOCK, nrows) * rl;
-  } else {
+  if (!uniform) {
 #pragma unroll
     for (int q = 0; q <= Q; ++q) rpv[q] = rowptr[r0 + min(tid + q * IPX_BLOCK, nrows)] - s;
   }
   CG_STAMP(3);
   ipx_lds_barrier();
   CG_STAMP(4);
-  // SpMV phase 1: products with the gathers served from the span
+  // SpMV phase 1: products with the gathers served from the span.  No test per entry: a lane
+  // beyond the tile's entries holds the tile's last one (the clamp of the loads) and leaves its
+  // product in a slot of prod[] that phase 2 does not read -- U gathers in flight, not U
+  // predicated round trips.  prod[] has a slot for every lane and u (the assert), and phase 2
+  // reads slots below e - s only: an irregular tile through rp[] <= e - s, a uniform one up to
+  // nrows rl, which is e - s by the way rowlen[] is made (cg_fused.compact_columns: rl >= 0 only
+  // where every row of the tile has rl entries).  (An empty tile holds another tile's entry:
+  // its column is not this span's.)
+  static_assert(U * IPX_BLOCK == FT_NNZ, "one slot of prod[] per lane and product");
+  if (e > s) {
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int jj = s + tid + u * IPX_BLOCK;
-    if (jj < e) prod[jj - s] = v[u] * span[c[u]];
+    for (int u = 0; u < U; ++u) prod[tid + u * IPX_BLOCK] = v[u] * span[c[u]];
   }
+  if (!uniform) {
 #pragma unroll
-  for (int q = 0; q <= Q; ++q) {
-    const int i = tid + q * IPX_BLOCK;
-    if (i <= nrows) rp[i] = rpv[q];
+    for (int q = 0; q <= Q; ++q) {
+      const int i = tid + q * IPX_BLOCK;
+      if (i <= nrows) rp[i] = rpv[q];
+    }
   }
   ipx_lds_barrier();
   CG_STAMP(5);
   // phase 2: row sums, diagonal term, partials of y'y and p'y
-  double acc_yy = 0.0, acc_xy = 0.0, yq[Q];
+  double acc_yy = 0.0, acc_xy = 0.0, yq[Q], sums[Q];
+  if (uniform) {
+    // entry k of the lane's Q rows together (a lane beyond the tile's rows sums the last row's,
+    // for nobody): one trip count for the workgroup, Q reads in flight
+    const double *pq[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      pq[q] = prod + min(tid + q * IPX_BLOCK, max(nrows - 1, 0)) * rl;
+      sums[q] = 0.0;
+    }
+#pragma unroll 1
+    for (int k = 0; k < rl; ++k) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) sums[q] += pq[q][k];
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int i = tid + q * IPX_BLOCK;
+      double sum = 0.0;
+      if (i < nrows) {
+        const int a = rp[i], b = rp[i + 1];
+        for (int k = a; k < b; ++k) sum += prod[k];
+      }
+      sums[q] = sum;
+    }
+  }
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
     const int i = tid + q * IPX_BLOCK;
     yq[q] = 0.0;
     if (i < nrows) {
-      const int a = rp[i], b = rp[i + 1];
-      double sum = 0.0;
-      for (int k = a; k < b; ++k) sum += prod[k];
+      const double sum = sums[q];
       const double xr = span[r0 - c_lo + i];
       double y = 1.0 * sum;
       if (HAS_DIAG) y += dg[q] * xr;

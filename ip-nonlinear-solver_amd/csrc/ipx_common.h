@@ -91,6 +91,21 @@ __device__ __forceinline__ int ipx_xcd_item(int block, int nitems) {
   return ((block >> 3) < per && t < nitems) ? t : -1;
 }
 
+// ---- workgroup-uniform base + 32-bit lane offset ------------------------------
+// Element `off` behind `base`, with the byte offset formed in 32 bits.  Where `base` is the same
+// in every lane (a kernel argument advanced by values every lane reads alike: the workgroup's
+// tile, span or window) the access takes its scalar-base form -- the base in two SGPRs, the
+// lane's offset in one VGPR -- instead of a 64-bit vector address formed by a sign extension
+// and a v_lshl_add_u64 per access.  `off` counts elements from the advanced base, so it is
+// bounded by the tile and not by the problem: off * sizeof(T) < 2^32 is the caller's.  `off` is
+// unsigned: there is no element before `base` -- a negative int wraps to an address far behind
+// it, so every lane that forms the reference clamps its offset first (an unsigned minimum
+// against the count), also a lane whose result is selected away afterwards.
+template <class T>
+__device__ __forceinline__ T &ipx_at(T *base, unsigned off) {
+  return *(T *)((const char *)base + off * (unsigned)sizeof(T));
+}
+
 // ---- fixed-order reductions -------------------------------------------
 // Wave: DPP butterfly inside each row of 16 lanes (xor 1, xor 2, half-row
 // mirror, row mirror: four v_mov_dpp pairs, no LDS crossbar), then the four
