@@ -1267,6 +1267,49 @@ int ipx_nd_dropped_fold(int64_t m, int32_t q, const double *Y, const int32_t *d_
 int ipx_nd_dropped_fill(int64_t m, int32_t q, const double *part, const int32_t *d_rows,
                         const int32_t *mark, const double *u, double *out, void *stream);
 
+/* ---- projected GLTR (csrc/gltr.hip, ipsolver/gltr.py) ----
+ * The Lanczos recurrence of the Generalized Lanczos Trust Region method on vectors of n doubles,
+ * with the trust-region problem of its tridiagonal T solved on the device after every step.
+ * Q: (kmax + 1) columns of n doubles, column j at Q + j n.  State block
+ * (ipx_gltr_state_doubles(kmax) doubles, written by ipx_gltr_start):
+ *   [0] stop code (0 running, 4 tolerance or invariant subspace, 1 cap), [1] vectors used k,
+ *   [2] gamma_0, [3] R, [4] tol, [5] lambda, [6] ||h||, [7] q_T(h) = 1/2 h'T h + gamma_0 h_0,
+ *   [8] gamma_{k+1}, [9] case (0 interior, 1 boundary, 2 near-hard), [10] cap,
+ *   [11] exit path of the tridiagonal solve (0 interior, 1 secular iteration converged,
+ *   2 near-hard, 3 collapsed bracket), [12] its rounds, [13] the last delta, [14..15] spare,
+ *   [16...] diag[kmax] (delta_j), off[kmax] (gamma_{j+1}), h[kmax].
+ * Every reduction is per-workgroup partials (part: ipx_gltr_part_doubles(n) doubles) folded in a
+ * fixed order by the consumer; no atomics.  Host arguments do not change from step to step, so
+ * steps are enqueued blind: once the stop code is set every launch of a later step returns at
+ * once and leaves state and Q as they are. */
+#define IPX_GLTR_MAX_VECTORS 256
+int64_t ipx_gltr_state_doubles(int32_t kmax);
+int ipx_gltr_grid(int64_t n);
+int64_t ipx_gltr_part_doubles(int64_t n);
+/* gamma_0 = ||g||, q_0 = g / gamma_0 into column 0, the header (tol < 0: the default
+ * max(min(0.01 gamma_0, 0.1 gamma_0^2), 1e-25); gamma_0^2 < tol stops at once with code 4, no
+ * vector used); cap <= kmax bounds the vectors.  Two launches. */
+int ipx_gltr_start(int64_t n, int32_t kmax, int32_t cap, const double *g, double *Q, double *state,
+                   double *part, double radius, double tol, void *stream);
+/* one step from w = Z H q_k (k read from the state on the device): delta_k = q_k'w,
+ * column k + 1 <- (w - delta_k q_k) - gamma_k q_{k-1} (no gamma term at k = 0), gamma_{k+1} its
+ * norm, T extended, h = argmin 1/2 h'T h + gamma_0 h_0 over ||h|| <= R, stop when
+ * (gamma_{k+1} h_k)^2 < tol, gamma_{k+1} <= 1e-14 gamma_0 or k + 1 reaches the cap; otherwise
+ * column k + 1 /= gamma_{k+1}.  Four launches. */
+int ipx_gltr_step(int64_t n, int32_t kmax, const double *w, double *Q, double *state, double *part,
+                  void *stream);
+/* x[i] = (x0 ? x0[i] : 0) + sum_{j < k} h[j] Q[j n + i], j ascending, separate multiply and add;
+ * 16-byte accesses when n is even and Q, x0, x are 16-byte aligned.  One launch. */
+int ipx_gltr_combine(int64_t n, int32_t kmax, const double *Q, const double *state,
+                     const double *x0, double *x, void *stream);
+/* The tridiagonal trust-region solve alone: diag[k], off[k - 1] (> 0), g0 > 0, radius > 0;
+ * out[0..5] = lambda, ||h||, q_T(h), case, exit path, rounds, out[8 ... 8 + k) = h.  The host twin
+ * runs the same routine with the device's lanes one after the other. */
+int ipx_gltr_tridiag(int32_t k, const double *diag, const double *off, double g0, double radius,
+                     double *out, void *stream);
+int ipx_gltr_tridiag_host(int32_t k, const double *diag, const double *off, double g0,
+                          double radius, double *out);
+
 #ifdef __cplusplus
 }
 #endif

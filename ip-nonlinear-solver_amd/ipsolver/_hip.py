@@ -186,6 +186,12 @@ _SIGNATURES = {
     "ipx_nd_dropped_fill": [_I64, _I32, _P, _P, _P, _P, _P, _P],
     "ipx_fd_assemble_sym": [_I64, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
                             _I32, _P, _P],
+    "ipx_gltr_grid": [_I64],
+    "ipx_gltr_start": [_I64, _I32, _I32, _P, _P, _P, _P, _F64, _F64, _P],
+    "ipx_gltr_step": [_I64, _I32, _P, _P, _P, _P, _P],
+    "ipx_gltr_combine": [_I64, _I32, _P, _P, _P, _P, _P],
+    "ipx_gltr_tridiag": [_I32, _P, _P, _F64, _F64, _P, _P],
+    "ipx_gltr_tridiag_host": [_I32, _P, _P, _F64, _F64, _P],
 }
 _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_launch_count": _c.c_longlong, "ipx_read_count": _c.c_longlong,
@@ -204,6 +210,7 @@ _RESTYPES = {"ipx_version": _c.c_char_p, "ipx_last_error": _c.c_char_p,
              "ipx_qr_padded_cols": _I64, "ipx_qr_ws_doubles": _I64,
              "ipx_qrp_ws_doubles": _I64, "ipx_qrp_info_doubles": _I64,
              "ipx_qrp_info_ints": _I64,
+             "ipx_gltr_state_doubles": _I64, "ipx_gltr_part_doubles": _I64,
              "ipx_rguard_start": _F64, "ipx_rguard_step_x": _F64, "ipx_rguard_step_q": _F64}
 _EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
                    "ipx_rguard_start": [_F64], "ipx_rguard_step_x": [_F64, _F64, _F64],
@@ -211,6 +218,7 @@ _EXTRA_ARGTYPES = {"ipx_blocktri_ws_doubles": [_I64, _I32],
                    "ipx_qr_padded_cols": [_I64], "ipx_qr_ws_doubles": [_I64, _I64],
                    "ipx_qrp_ws_doubles": [_I64, _I64], "ipx_qrp_info_doubles": [_I64],
                    "ipx_qrp_info_ints": [_I64],
+                   "ipx_gltr_state_doubles": [_I32], "ipx_gltr_part_doubles": [_I64],
                    "ipx_nd_symbolic": [_I64, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64],
                    "ipx_blockwide_ws_doubles": [_I64, _I32],
                    "ipx_banded_create": [_I64, _I32, _I32], "ipx_banded_destroy": [_P],

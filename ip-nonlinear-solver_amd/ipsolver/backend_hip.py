@@ -384,4 +384,5 @@ def projections(A, method=None):
 
 modified_dogleg = qp.modified_dogleg
 projected_cg = qp.projected_cg
+projected_gltr = qp.projected_gltr
 box_intersections = qp.box_intersections

@@ -298,6 +298,40 @@ def _minimize_distributed(fun, x0, grad, hess, constraints, method, xtol, gtol, 
         **options)
 
 
+def _subproblem_options(options, method, constraints, sharded):
+    """``options['subproblem']`` ('steihaug', the default, or 'gltr': the tangential step from
+    projected GLTR, ipsolver/gltr.py) and ``options['gltr_max_vectors']``: checked before any
+    device work.  The default leaves ``options`` without either key -- the same stages, the
+    same launches as before the option existed; 'gltr' passes both on to the SQP."""
+    from .gltr import check_max_vectors
+    subproblem = options.pop("subproblem", "steihaug")
+    max_vectors = check_max_vectors(options.pop("gltr_max_vectors", 64))
+    if subproblem not in ("steihaug", "gltr"):
+        raise ValueError("options['subproblem'] must be 'steihaug' or 'gltr', got %r"
+                         % (subproblem,))
+    if subproblem == "steihaug":
+        return
+    if sharded:
+        raise NotImplementedError("subproblem=%r: the row-sharded backend runs its own projected "
+                                  "CG loop; the option is available on one GPU only"
+                                  % (subproblem,))
+    if method is None:
+        def is_equality(c):
+            kind = getattr(c, "kind", None)
+            return (kind if isinstance(kind, str) else kind[0]) == "equals"
+        resolved = ('equality_constrained_sqp'
+                    if all(is_equality(c) for c in _constraint_list(constraints))
+                    else 'tr_interior_point')
+    else:
+        resolved = _METHODS.get(method)
+    if resolved == 'tr_interior_point':
+        raise ValueError("subproblem='gltr' with method 'tr_interior_point': every barrier "
+                         "subproblem carries the slack box and projected GLTR handles the sphere "
+                         "only, so the option would do nothing; use it with "
+                         "'equality_constrained_sqp'")
+    options["subproblem"], options["gltr_max_vectors"] = subproblem, max_vectors
+
+
 def _constraint_list(constraints):
     if isinstance(constraints, (NonlinearConstraint, LinearConstraint, BoxConstraint)):
         return [constraints]
@@ -450,6 +484,8 @@ def _minimize_constrained(fun, x0, grad, hess, constraints, method, xtol, gtol, 
                           options, callback, max_iter, verbose):
     options = dict(options)
     shard = _shard_request(options)
+    _subproblem_options(options, method, constraints,
+                        shard or (hasattr(x0, "sh") and hasattr(x0, "owns")))
     if _qn.is_strategy(hess) and options.get("constant_hessian", False):
         raise ValueError("options={'constant_hessian': True} cannot be combined with a "
                          "quasi-Newton hess (%r): its approximation changes at every step" % (hess,))

@@ -22,7 +22,7 @@ from .device import DVec
 
 __all__ = ['sphere_intersections', 'box_intersections', 'box_sphere_intersections',
            'inside_box_boundaries', 'reinforce_box_boundaries', 'modified_dogleg',
-           'projected_cg']
+           'projected_cg', 'projected_gltr']
 
 _TINY = 1e-25   # CLOSE_TO_ZERO, qp_subproblem.py:496
 _INF = float("inf")
@@ -308,3 +308,6 @@ def projected_cg(H, c, Z, Y, b, trust_radius=np.inf, lb=None, ub=None, tol=None,
     if return_all:
         info['allvecs'] = allvecs
     return x, info
+
+
+from .gltr import projected_gltr      # noqa: E402  (the GLTR twin of projected_cg: gltr.py)

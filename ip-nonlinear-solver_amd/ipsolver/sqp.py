@@ -78,8 +78,11 @@ class _Box:
 class HostStages:
     """The stages through the backend's vector operations; scalars of a stage read together."""
 
-    def __init__(self, xp, box):
+    def __init__(self, xp, box, subproblem="steihaug", gltr_max_vectors=64):
         self.xp, self.box = xp, box
+        # "gltr": the tangential step of a problem without a box from projected GLTR (gltr.py)
+        self.subproblem, self.gltr_max_vectors = subproblem, gltr_max_vectors
+        self.gltr_calls = self.gltr_boundary_calls = 0
 
     # -- settle
     def settle(self, pt, method):
@@ -114,7 +117,13 @@ class HostStages:
         c_t = H.dot(dn) + pt.c
         lb_t = box.lb - dn if box.lb is not None else None
         ub_t = box.ub - dn if box.ub is not None else None
-        dt, info = xp.projected_cg(H, c_t, pt.Z, pt.Y, None, q[RADIUS_T], lb_t, ub_t)
+        if self.subproblem == "gltr" and lb_t is None and ub_t is None:
+            dt, info = xp.projected_gltr(H, c_t, pt.Z, pt.Y, None, q[RADIUS_T],
+                                         max_vectors=self.gltr_max_vectors)
+            self.gltr_calls += 1
+            self.gltr_boundary_calls += 1 if info['hits_boundary'] else 0
+        else:
+            dt, info = xp.projected_cg(H, c_t, pt.Z, pt.Y, None, q[RADIUS_T], lb_t, ub_t)
         if hasattr(xp, "note_cg_length"):
             xp.note_cg_length(info['niter'])
         d = dn + dt
@@ -427,7 +436,14 @@ def _same_key(a, b):
     return a[0] == b[0] and all(x[0] is y[0] and x[1] == y[1] for x, y in zip(a[1:], b[1:]))
 
 
-def _stages(xp, n, m, x0, box):
+def _stages(xp, n, m, x0, box, subproblem="steihaug", gltr_max_vectors=64):
+    if subproblem == "gltr":
+        # (the device chains have the Steihaug loop built in: host-driven stages, as under the
+        # no-step-chain form)
+        if not hasattr(xp, "projected_gltr"):
+            raise NotImplementedError("subproblem='gltr': this backend has no projected GLTR; "
+                                      "the option is available on one GPU only")
+        return HostStages(xp, box, subproblem, gltr_max_vectors)
     host = HostStages(xp, box)
     if getattr(xp, "name", None) == "hip" and m > 0 and hasattr(x0, "t") \
             and not _chain_disabled():
@@ -444,10 +460,15 @@ def equality_constrained_sqp(fun_and_constr, grad_and_jac, lagr_hess, x0, fun0, 
                              constr0, jac0, stop_criteria, state, xp,
                              trust_lb=None, trust_ub=None, initial_penalty=1.0,
                              initial_trust_radius=1.0, scaling=None, return_all=False,
-                             factorization_method=None):
+                             factorization_method=None, subproblem="steihaug",
+                             gltr_max_vectors=64):
+    if subproblem not in ("steihaug", "gltr"):
+        raise ValueError("subproblem must be 'steihaug' or 'gltr', got %r" % (subproblem,))
     n, m = len(x0), len(constr0)
     box = _Box(xp, n, trust_lb, trust_ub)
-    stages = _stages(xp, n, m, x0, box)
+    stages = _stages(xp, n, m, x0, box, subproblem, gltr_max_vectors)
+    if subproblem == "gltr":
+        state.gltr_calls = state.gltr_boundary_calls = 0
     if state.niter == 0:
         # a new solve starts from the same launch plan whatever ran before it: its first normal
         # step is expected long, its first Hessian keeps its diagonal apart (backend_hip
@@ -512,6 +533,9 @@ def equality_constrained_sqp(fun_and_constr, grad_and_jac, lagr_hess, x0, fun0, 
         state.trust_radius, state.penalty = radius, penalty
         state.cg_niter += trial.cg_info["niter"]
         state.cg_info = trial.cg_info
+        if subproblem == "gltr":
+            state.gltr_calls = stages.gltr_calls
+            state.gltr_boundary_calls = stages.gltr_boundary_calls
         if return_all:
             state.allvecs.append(xp.copy(pt.x))
             state.allmult.append(xp.copy(pt.v))
