@@ -496,10 +496,10 @@ constexpr double XS_BAND = 1e-9; // the carried form decides :583 only outside t
 // (ipx_xsums_job).  The launcher picks it only for launches that do; every other launch -- the
 // trust_radius = inf loop, the stand-alone entry, BOX, PEER -- runs the kernel without them.
 // GUARD: the radius guard's instantiation -- the kernel of the trust_radius = inf loop (no
-// ||x + alpha p||^2 partials, no sums, a four-way block sum) that decides :583 from the bound T
-// every workgroup loads with its state words (xs.in: the guard's three words).  Without mode
-// bit 1 a bound that is not below the radius stops the batch (IPX_CG_STOP_GUARD_LOST); with it
-// (a resumed iteration whose test was taken) the bounds advance all the same.
+// ||x + alpha p||^2 partials, no sums; a two-way block sum, gg and tt) that decides :583 from the
+// bound T every workgroup loads with its state words (xs.in: the guard's three words).  Without
+// mode bit 1 a bound that is not below the radius stops the batch (IPX_CG_STOP_GUARD_LOST); with
+// it (a resumed iteration whose test was taken) the bounds advance all the same.
 template <bool HAS_DIAG, int Q, int QS, bool BOX, bool C16, bool PEER, bool XSUM = false,
           bool GUARD = false>
 __global__ void __launch_bounds__(IPX_BLOCK)
@@ -561,6 +561,8 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   if (BOX) foldC.load(partsC, countsC);
   const int r0 = tiles[tile], r1 = tiles[tile + 1];
   const int s = tiles[ntiles + 1 + tile], e = tiles[ntiles + 2 + tile];
+  // (requested with the tile's bounds, ahead of the value loads: one wait for all of them)
+  const int rl = C16 ? rowlen[tile] : -1;       // >= 0: every row of the tile has rl entries
   const int nrows = r1 - r0;
   const int c_lo = max(r0 - hmax, 0), c_hi = min(r1 + hmax, n);
   const int nspan = c_hi - c_lo;
@@ -574,7 +576,6 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
     c[u] = C16 ? (int)col16[jj] : colidx[jj] - c_lo;
     v[u] = val[jj];
   }
-  const int rl = C16 ? rowlen[tile] : -1;       // >= 0: every row of the tile has rl entries
   // span operands: element j of the span is column c_lo + j
   double sp[QS], sg[QS];
   const double *pbl = pb_in + (int64_t)(tile - 1) * 2 * hmax + hmax;   // right part of tile-1
@@ -620,6 +621,15 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   }
   if constexpr (XS) {
     ipx_block_sum_multi<5>(loc, lds, red);
+  } else if constexpr (GUARD) {
+    // neither xn2 nor a violation count is formed or read: gg and tt alone go through the block
+    // sum (ipx_block_sum_multi sums every component by itself -- the lanes of a wave, then the
+    // waves in wave order -- so their bits do not depend on how many travel together)
+    double l2[2] = {loc[2], loc[3]}, r2[2];
+    ipx_block_sum_multi<2>(l2, lds, r2);
+    red[0] = red[1] = red[4] = 0.0;
+    red[2] = r2[0];
+    red[3] = r2[1];
   } else {
     double l4[4] = {loc[0], loc[1], loc[2], loc[3]}, r4[4];
     ipx_block_sum_multi<4>(l4, lds, r4);
