@@ -375,7 +375,10 @@ typedef struct ipx_cg_args {
    * H_col16 = one uint16 per nonzero, its column as an offset into the row tile's span
    * (col - max(tile's first row - H_hmax, 0)); H_rowlen = one int per row tile, the common
    * length of its rows or -1 (then H_rowptr is read for that tile).  Same arithmetic; 2 B
-   * instead of 4 per nonzero and no row pointers on uniform tiles. */
+   * instead of 4 per nonzero and no row pointers on uniform tiles.  A uniform, non-empty tile
+   * whose entry k of row i has the offset H_col16[tile's first entry] + i + k may carry bit 16
+   * (0x10000) in its word: under the radius guard the kernel then forms the tile's offsets and
+   * reads that one entry of H_col16 alone; every other form ignores the bit. */
   const void *H_col16;
   const int32_t *H_rowlen;
   /* The same for the fused step1 + A.r kernel (A_span > 0, standard tiles):

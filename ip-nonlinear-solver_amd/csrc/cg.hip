@@ -484,6 +484,11 @@ constexpr double XS_BAND = 1e-9; // the carried form decides :583 only outside t
 // per pattern by the host binding) and the row pointers of a tile whose rows all have the
 // same length are not read at all (rowlen[tile] >= 0): 2 + 4/rowlen bytes less per nonzero of
 // the 12 a CSR entry costs -- 10 of the 96 MB this kernel moves at n = 1e6.
+// A tile whose entry k of row i sits at span offset col16[s] + i + k (every interior tile of a
+// banded Hessian) carries ROWLEN_SHIFTED in its rowlen[] word (cg_fused.flagged_rowlen): the GUARD
+// form then reads col16[s] alone and forms the other offsets -- the table's 2 bytes per nonzero
+// less.  Every other form masks the flag and reads the table (plain and XSUM measured slower
+// with the offsets formed: DESIGN.md section 6; BOX and PEER were not tried).
 // PEER (row-sharded loop on the peer mailboxes, one segment): p2 / p3 / p4 are the rank's OWN
 // ranges of the partial arrays; every workgroup folds them, workgroup 0 sends the four sums to
 // the peers and every workgroup adds up the ranks' contributions in rank order (ipx_peer_sum)
@@ -500,6 +505,22 @@ constexpr double XS_BAND = 1e-9; // the carried form decides :583 only outside t
 // bound T every workgroup loads with its state words (xs.in: the guard's three words).  Without
 // mode bit 1 a bound that is not below the radius stops the batch (IPX_CG_STOP_GUARD_LOST); with
 // it (a resumed iteration whose test was taken) the bounds advance all the same.
+constexpr int ROWLEN_SHIFTED = 1 << 16;      // cg_fused.ROWLEN_SHIFTED (row lengths lie below it)
+
+constexpr int SHIFT_MAX_RL = 8;              // longest row the kernel forms offsets for
+
+// the span offsets of a lane's entries in a flagged tile of RL-entry rows; c[u] comes in as
+// the tile's first offset
+template <int RL, int U>
+__device__ __forceinline__ void shifted_offsets(int (&c)[U], int tid, int last) {
+  static_assert(RL >= 1 && RL <= SHIFT_MAX_RL, "a case of the switch in k_cg_step2_hp");
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const unsigned d = (unsigned)min(tid + u * IPX_BLOCK, last);
+    c[u] += (int)(d - (RL - 1) * (d / RL));
+  }
+}
+
 template <bool HAS_DIAG, int Q, int QS, bool BOX, bool C16, bool PEER, bool XSUM = false,
           bool GUARD = false>
 __global__ void __launch_bounds__(IPX_BLOCK)
@@ -514,6 +535,7 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
               const uint16_t *__restrict__ col16, const int32_t *__restrict__ rowlen,
               typename peer_arg<PEER>::type pj, double *g_halo, ipx_xsums_job xs) {
   constexpr bool XS = XSUM;                    // the carried sums of the radius test
+  constexpr bool SHIFT = C16 && GUARD;         // flagged tiles form their column offsets
   static_assert(!XSUM || (!BOX && !PEER), "carried sums: no box, one GPU");
   static_assert(!GUARD || (!BOX && !PEER && !XSUM), "radius guard: no box, one GPU, no sums");
   // (the folded sums ride in the three loads per lane of the xn2 partials: ipx_fold_regs<2, 3>)
@@ -562,7 +584,8 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   const int r0 = tiles[tile], r1 = tiles[tile + 1];
   const int s = tiles[ntiles + 1 + tile], e = tiles[ntiles + 2 + tile];
   // (requested with the tile's bounds, ahead of the value loads: one wait for all of them)
-  const int rl = C16 ? rowlen[tile] : -1;       // >= 0: every row of the tile has rl entries
+  const int rlf = C16 ? rowlen[tile] : -1;
+  const int rl = rlf < 0 ? -1 : rlf & (ROWLEN_SHIFTED - 1);   // >= 0: every row of the tile has rl entries
   const int nrows = r1 - r0;
   const int c_lo = max(r0 - hmax, 0), c_hi = min(r1 + hmax, n);
   const int nspan = c_hi - c_lo;
@@ -570,10 +593,15 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   constexpr int U = FT_NNZ / IPX_BLOCK;
   int c[U];
   double v[U];
+  // a flagged tile (cg_fused.shifted_tiles_np; never empty) with a row length phase 1 has a
+  // case for: every offset load of the workgroup takes the tile's FIRST offset -- one line, no
+  // table traffic -- and phase 1 adds the entry's own part.  (Loads at a selected address, not a
+  // branch around them: the prologue stays one block, and it measured 0.02-0.18 us shorter.)
+  const bool formed = SHIFT && rlf >= ROWLEN_SHIFTED && rl <= SHIFT_MAX_RL;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int jj = min(s + tid + u * IPX_BLOCK, max(e - 1, 0));   // empty tile: any valid entry
-    c[u] = C16 ? (int)col16[jj] : colidx[jj] - c_lo;
+    c[u] = C16 ? (int)col16[formed ? s : jj] : colidx[jj] - c_lo;
     v[u] = val[jj];
   }
   // span operands: element j of the span is column c_lo + j
@@ -796,6 +824,23 @@ k_cg_step2_hp(int n, double *st, int parity, int mode, const double *__restrict_
   // where every row of the tile has rl entries).  (An empty tile holds another tile's entry:
   // its column is not this span's.)
   static_assert(U * IPX_BLOCK == FT_NNZ, "one slot of prod[] per lane and product");
+  if constexpr (SHIFT) {
+    // entry d = i rl + k of a flagged tile sits at span offset col16[s] + i + k =
+    // c0 + d - (rl - 1)(d / rl): rl is the workgroup's, the divisors are constants
+    if (formed) {
+      const int last = e - 1 - s;
+      switch (rl) {
+        case 1: shifted_offsets<1>(c, tid, last); break;
+        case 2: shifted_offsets<2>(c, tid, last); break;
+        case 3: shifted_offsets<3>(c, tid, last); break;
+        case 4: shifted_offsets<4>(c, tid, last); break;
+        case 5: shifted_offsets<5>(c, tid, last); break;
+        case 6: shifted_offsets<6>(c, tid, last); break;
+        case 7: shifted_offsets<7>(c, tid, last); break;
+        default: shifted_offsets<8>(c, tid, last); break;
+      }
+    }
+  }
   if (e > s) {
 #pragma unroll
     for (int u = 0; u < U; ++u) prod[tid + u * IPX_BLOCK] = v[u] * span[c[u]];
@@ -1474,6 +1519,8 @@ template <bool PEER> Step1ArFn<PEER> step1_ar_kernel(int qs, int xn, bool c16) {
 //            need the fused step1, which a box excludes (a box wins: XSUM is not looked at);
 //            GUARD x C16 0, 1 without BOX and XSUM (the radius guard, where XSUM would apply)
 //   PEER     BOX 0, 1 with C16 only (peer_fusable), never XSUM (the carried sums are one GPU's)
+//   The four GUARD x C16 instantiations form the column offsets of flagged tiles
+//   (ROWLEN_SHIFTED); no instantiation was added for that.
 template <bool PEER> using Step2HpFn = decltype(&k_cg_step2_hp<true, 4, 5, false, true, PEER>);
 template <bool PEER, bool D, int Q, int QS>
 Step2HpFn<PEER> step2_hp_forms(bool box, bool c16, bool xsum, bool guard) {

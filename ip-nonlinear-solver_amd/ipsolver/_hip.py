@@ -309,7 +309,9 @@ def load():
 #                      in every iteration, never from the norm bound (ipx_cg_args.radius_guard
 #                      stays 0)
 #   table-columns      the fused projection reads the 16-bit column offsets of A even where every
-#                      row is a run of consecutive columns (ipx_cg_args.A_contig stays 0)
+#                      row is a run of consecutive columns (ipx_cg_args.A_contig stays 0), and
+#                      the fused step2 + H.p kernel those of H on shifted-contiguous row tiles
+#                      (ipx_cg_args.H_rowlen carries no flag bit)
 DEBUG_FORMS = ("no-fuse", "no-resident", "no-compact-groups", "no-affine-groups", "keep-xn2",
                "read-xn2", "pack-comm", "no-post-tail", "no-step-chain", "no-lowrank-loop",
                "no-fused-projection", "table-columns", "no-radius-guard")

@@ -183,6 +183,69 @@ def compact_columns(pattern, hmax):
     return out
 
 
+ROWLEN_SHIFTED = 1 << 16          # csrc/cg.hip ROWLEN_SHIFTED: flag bit of the per-tile table
+
+
+def shifted_tiles_np(col16, rowlen, bounds):
+    """Which uniform row tiles are *shifted-contiguous*: entry k of row i of the tile sits at
+    span offset ``col16[s] + i + k`` (every interior tile of a banded pattern whose rows are runs
+    of consecutive columns, one column further per row), so that the fused step2 + H.p kernel
+    forms the offsets instead of loading them.  numpy in, numpy out: ``col16`` the offsets per
+    nonzero, ``rowlen`` per tile the common row length or -1, ``bounds`` the ntiles + 1 entry
+    boundaries of the tiles.  Returns one bool per tile (False for irregular and empty tiles)."""
+    off = np.asarray(col16).astype(np.int64)
+    rl = np.asarray(rowlen).astype(np.int64)
+    b = np.asarray(bounds).astype(np.int64)
+    s, cnt = b[:-1], np.diff(b)
+    flag = (rl > 0) & (cnt > 0)
+    if not flag.any():
+        return flag
+    tile = np.repeat(np.arange(len(rl)), cnt)
+    d = np.arange(b[0], b[-1]) - s[tile]
+    rle = np.maximum(rl, 1)[tile]
+    ok = off[b[0]:b[-1]] == off[s[tile]] + d // rle + d % rle
+    full = np.flatnonzero(cnt > 0)
+    flag[full] &= np.logical_and.reduceat(ok, s[full] - b[0])
+    return flag
+
+
+def flagged_rowlen(pattern, hmax):
+    """The per-tile table ``k_cg_step2_hp`` takes in ``rowlen``'s place: ``compact_columns``'s
+    row lengths with ``ROWLEN_SHIFTED`` set on the shifted-contiguous tiles.  Symbolic; cached
+    on the pattern."""
+    key = ("_ipx_rowlen_flagged", int(hmax))
+    cache = getattr(pattern, "_ipx_rowlen_flagged", None)
+    if cache is not None and cache[0] == key:
+        return cache[1]
+    col16, rowlen = compact_columns(pattern, hmax)
+    nt = pattern.ntiles
+    rl = rowlen.cpu().numpy()
+    flag = shifted_tiles_np(col16.cpu().numpy().view(np.uint16), rl,
+                            pattern.tiles_h[nt + 1:2 * nt + 2])
+    out = torch.from_numpy(np.where(flag, rl | ROWLEN_SHIFTED, rl).astype(np.int32)).to(rowlen.device)
+    pattern._ipx_rowlen_flagged = (key, out)
+    return out
+
+
+ROWT_MAX_RL = 4         # longest row of a tile stored entry-major (rowmajor_tiles_map_np)
+
+
+def rowmajor_tiles_map_np(rowlen, shifted, bounds):
+    """Gather map of the tile-transposed value order: ``valT = val[map]`` holds the values of a
+    shifted-contiguous tile of rows of ``rl <= ROWT_MAX_RL`` entries entry-major inside the
+    tile's own range, ``valT[s + k nrows + i] = val[s + i rl + k]`` (lane i then loads entry k of
+    its row next to its neighbours'), and every other tile in CSR order.  numpy in, numpy out;
+    arguments as ``shifted_tiles_np``'s, ``shifted`` its result."""
+    rl = np.asarray(rowlen).astype(np.int64)
+    b = np.asarray(bounds).astype(np.int64)
+    gmap = np.arange(b[-1], dtype=np.int64)
+    for t in np.flatnonzero(np.asarray(shifted) & (rl <= ROWT_MAX_RL)):
+        s, e = b[t], b[t + 1]
+        nrows = (e - s) // rl[t]
+        gmap[s:e] = s + np.arange(e - s).reshape(nrows, rl[t]).T.ravel()
+    return gmap
+
+
 def fuse_own(pattern, tile_nnz=None):
     """Column ownership for the fused step1 + A.r kernel (csrc/cg.hip k_cg_step1_ar):
     ``(own, span, tiles, ntiles)`` or None.  Qualifies when every row tile is on the
@@ -726,6 +789,10 @@ class _Loop:
             th = Hc.pattern.tiles_h
             a.H_tile_rows = int(np.max(np.diff(th[:Hc.pattern.ntiles + 1])))
             self.H_col16, self.H_rowlen = compact_columns(Hc.pattern, hmax)
+            # shifted-contiguous tiles (every interior tile of a banded Hessian) carry a flag:
+            # the kernel forms their offsets from the tile's first one and reads no table
+            if not _hip.debug_form("table-columns"):
+                self.H_rowlen = flagged_rowlen(Hc.pattern, hmax)
             a.H_col16, a.H_rowlen = _ptr(self.H_col16), _ptr(self.H_rowlen)
         # banded Jacobian, no box: step1 rides inside the A.r SpMV
         own = None if (no_fuse or lb is not None or m == 0) else fuse_own(A.pattern)
