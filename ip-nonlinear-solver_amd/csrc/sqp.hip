@@ -35,7 +35,9 @@
 #include <vector>
 
 // ---- the block ----------------------------------------------------------------------------
-// (mirrored by ipsolver/sqp.py; doubles)
+// (mirrored by ipsolver/sqp.py; doubles.  Which entry point writes which entries -- and leaves
+// every other one alone -- is listed in ONE place, tests/sqp_chain_cases.py OWNED, and held by
+// tests/test_gpu_sqp_chain_stages.py)
 enum {
   SQ_RADIUS = 0,        // trust radius: in; out of `radius` (the ladder's result)
   SQ_PENALTY = 1,       // penalty: in; raised by `model`, restored by `radius` on a rejection
